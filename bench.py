@@ -213,6 +213,10 @@ class C2(object):
     def step(self, s):
         self.res = self.al.locate_batch(self.batches[s % len(self.batches)], self.filtered)
 
+    def outputs(self):
+        """What the caller of the timed call received from the last step (--dump-outputs)."""
+        return {"records": self.res.records}
+
     def jit(self):
         """Is the pre-pass the timed steps ran the kernel compiled at run time for this aligner (jit.hpp)?"""
         return bool(self.filtered and self.batch.layout == "plane64" and self.al.prepare(150))
@@ -427,6 +431,9 @@ class C3(object):
     def step(self, s):
         self.res = self.ia.match_insert_batch(self.b1, self.b2)
 
+    def outputs(self):
+        return {"records": self.res.records}
+
     def describe(self):
         return {"workload": "%s: %d pairs 2 x %d bp per GPU, insert aligner (overlap + adapter match)%s, plane64-packed "
                             "reads resident in HBM" % (self.name, self.n, self.read_len,
@@ -501,6 +508,12 @@ class C5(C3):
             self.res = self.ia.match_insert_batch(d["b1"], d["b2"])
             self.be.insert_correct_batch(self.res.records, d["s1"], d["q1"], None, d["s2"], d["q2"], None, 2, 1, self.comp,
                                          self.changed, self.newlen, planes1=d["b1"], planes2=d["b2"])
+
+    def outputs(self):
+        """The records, the correction counts and lengths, and the last step's sub-batch corrected in place."""
+        d = self.batches[self.k - 1]
+        return {"records": self.res.records, "changed": self.changed, "newlen": self.newlen,
+                "seq1": d["s1"], "qual1": d["q1"], "seq2": d["s2"], "qual2": d["q2"]}
 
     def describe(self):
         d = C3.describe(self)
@@ -581,6 +594,10 @@ class C4(object):
         wc, front, back = be.linked_match_batch(self.lset._handle, self.batch.packed, self.batch.lens, self.batch.nreads,
                                                 self.batch.max_len)
         self.res = (wc[:, 0], wc[:, 1], front, back)
+
+    def outputs(self):
+        which, count, front, back = self.res
+        return {"which": which, "count": count, "front": front, "back": back}
 
     def describe(self):
         which, count, front, back = self.res
@@ -682,6 +699,26 @@ def device_name(ordinal):
     return "cpu" if EMU else "cuda:%d" % ordinal
 
 
+DUMP_BYTES = 64_000_000           # --dump-outputs: every .npy file of one invocation together
+DUMP_SEED = 0
+
+
+def dump_outputs(cfg, directory, budget):
+    """--dump-outputs: the arrays of cfg.outputs() (the last timed step) as DIRECTORY/<config>_<name>.npy, float32
+    (every value is an integer of magnitude below 2^24, so the conversion is exact).  All arrays have one row per read
+    or pair; when every row would not fit in `budget` bytes, the same fixed sample of rows is written for each of
+    them (numpy default_rng(DUMP_SEED), without replacement, in row order)."""
+    arrays = cfg.outputs()
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(4 * (t.numel() // max(1, t.shape[0])) for t in arrays.values())
+    rows = min(n, max(0, budget - 4096 * len(arrays)) // row_bytes)       # (4 KB per file for the .npy header)
+    idx = np.arange(n) if rows == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, rows, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        part = t.index_select(0, torch.from_numpy(idx).to(t.device)) if rows < n else t
+        np.save(os.path.join(directory, "%s_%s.npy" % (cfg.name, name)), part.cpu().numpy().astype(np.float32))
+
+
 def measure(cfg_cls, args, rank, world, local_rank, dist, headline, defer_secondary=False):
     """Build one config's workload, run warmup + EXACTLY args.steps timed steps (barrier + synchronize on both
     sides, HIP events on the launch stream around every step, max over ranks) and return its result dict
@@ -721,6 +758,8 @@ def measure(cfg_cls, args, rank, world, local_rank, dist, headline, defer_second
     dt_max = max(per_rank)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(cfg, args.dump_outputs, DUMP_BYTES // args.dump_configs)
 
     units = cargs.reads * cfg.unit_reads                         # reads per step and GPU
     wall_ms = dt_max / args.steps * 1e3
@@ -850,7 +889,7 @@ def measure_threads(cfg_cls, args, devices):
     with _lib.thread_backend(_lib.HipBackend(devices[0])):
         desc = cfg.describe()
     desc["parallelism"] = "shard%d" % world
-    return {
+    out = {
         "metric": cfg.metric, "value": units * world * args.steps / dt, "unit": "reads/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": cfg.dtype, "data": "synthetic",
@@ -860,6 +899,9 @@ def measure_threads(cfg_cls, args, devices):
                      "note": "per GPU; " + cfg.note(kms)},
         "per_rank_ms_per_step": [(e - b) / args.steps * 1e3 for b, e in zip(t_begin, t_end)],
     }
+    if args.dump_outputs:
+        dump_outputs(cfg, args.dump_outputs, DUMP_BYTES)          # the first device's shard
+    return out
 
 
 def self_launch(args):
@@ -965,7 +1007,13 @@ def main():
     ap.add_argument("--launcher", default=None, help=argparse.SUPPRESS)       # set by self_launch() for its ranks
     ap.add_argument("--full-sweep", action="store_true",
                     help="C2: time the unfiltered full-column DP kernel instead of the filtered pipeline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rank 0's shard) as DIR/<config>_<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed sample of rows, the same for every array of a config, "
+                         "when a config's outputs do not fit in its share)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.scaling:
         raise SystemExit(scaling_curve(args))
@@ -1021,6 +1069,7 @@ def main():
         _lib.set_backend(_lib.HipBackend(local_rank))
     head = args.config or "C2"
     with_others = args.config is None and args.others and not args.full_sweep
+    args.dump_configs = 4 if with_others else 1                  # configs that share the --dump-outputs budget
     line = measure(CONFIGS[head], args, rank, world, local_rank, dist, True, defer_secondary=with_others)
     if args.config is None and args.others and not args.full_sweep:
         # the other BASELINE configs on the same clock: same steps / warmup, one after the other, each with its
