@@ -182,6 +182,11 @@ PROTOTYPES = {
     "atr_fastq_emit_work_bytes": (C.c_size_t, [C.c_int64]),
     "atr_fastq_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "atr_read_stats_bytes": (C.c_int64, [C.c_int]),
+    "atr_read_stats_clear": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "atr_read_stats_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
+                             + [C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "atr_read_stats_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
 }
 
 FASTQ_ERR_AT, FASTQ_ERR_PLUS, FASTQ_ERR_NAME2, FASTQ_ERR_LENGTH = 1, 2, 3, 4
@@ -920,6 +925,32 @@ class HipBackend(object):
             if total:
                 _check(self.lib, self.lib.atr_fastq_emit(*args, _ptr(out), self._stream()), "atr_fastq_emit")
         return out[:total]
+
+    # -- read statistics (atr_read_stats_*) ---------------------------------------------------------------------
+    def read_stats_words(self, max_len):
+        """uint64 words of a statistics block for reads of up to ``max_len`` bases."""
+        return _check(self.lib, self.lib.atr_read_stats_bytes(int(max_len)), "atr_read_stats_bytes") // 8
+
+    def read_stats_clear(self, block, max_len):
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_read_stats_clear(_ptr(block), int(max_len), self._stream()),
+                   "atr_read_stats_clear")
+
+    def read_stats_batch(self, block, max_len, longest, quality_base, data, records, begin=None, end=None, ubegin=None,
+                         uend=None, dest=None, which=0, index_base=0):
+        """Adds the records (their kept intervals, masks and destination filter as atr_fastq_emit) into ``block``;
+        record r is read ``index_base + r`` of the stream."""
+        n = records.shape[0]
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_read_stats_batch(
+                _ptr(block), int(max_len), int(longest), int(quality_base), _ptr(data), _ptr(records), _ptr(begin),
+                _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(dest), int(which), n, int(index_base), self._stream()),
+                "atr_read_stats_batch")
+
+    def read_stats_merge(self, dst, dst_max_len, src, src_max_len, index_offset=0):
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_read_stats_merge(_ptr(dst), int(dst_max_len), _ptr(src), int(src_max_len),
+                                                           int(index_offset), self._stream()), "atr_read_stats_merge")
 
 
 _backend = None

@@ -33,6 +33,72 @@ DEST_NAMES = {_lib.DEST_KEEP: "keep", _lib.DEST_TOO_SHORT: "too_short", _lib.DES
               _lib.DEST_TOO_MANY_N: "too_many_n", _lib.DEST_TRIMMED: "trimmed", _lib.DEST_UNTRIMMED: "untrimmed"}
 
 
+# the names the reference's --stats post keys its destinations by (dest.name, commands/trim/filters.py); the
+# trimmed / untrimmed filters have none
+POST_STATS_NAMES = {_lib.DEST_KEEP: "NoFilter", _lib.DEST_TOO_SHORT: "too_short", _lib.DEST_TOO_LONG: "too_long",
+                    _lib.DEST_TOO_MANY_N: "too_many_n"}
+
+
+def _stats_modes(stats):
+    modes = (stats,) if isinstance(stats, str) else tuple(stats or ())
+    if any(m not in ("pre", "post") for m in modes):
+        raise ValueError("stats must be a sequence of 'pre' and 'post'")
+    return modes
+
+
+class TrimStats(object):
+    """``atropos trim --stats pre|post|both`` (StatsRecordHandlerWrapper, commands/trim/__init__.py:140-205) over
+    the device state of a run: pre-trim statistics of every chunk before the first stage, post-trim statistics of
+    what each destination receives, per destination name."""
+
+    def __init__(self, modes, paired, quality_base):
+        from . import stats as S
+        cls = S.PairedEndReadStatistics if paired else S.SingleEndReadStatistics
+        self.make = lambda: cls(qualities=True, quality_base=quality_base)
+        self.pre = self.make() if "pre" in modes else None
+        self.post = {} if "post" in modes else None
+
+    def add_post(self, counts, collect):
+        """``counts``: {destination name: reads} of a chunk; ``collect(stats, code)`` adds destination ``code``."""
+        if self.post is None:
+            return
+        codes = {name: code for code, name in DEST_NAMES.items()}
+        for name, v in counts.items():
+            if not v:
+                continue
+            if name == "merged":
+                raise NotImplementedError("post-trim statistics of merged pairs (the reference collects them with "
+                                          "read2 = None and fails)")
+            code = codes[name]
+            if code not in POST_STATS_NAMES:
+                raise NotImplementedError("post-trim statistics of the reads the %s filter takes (the reference's "
+                                          "filter has no name)" % name)
+            key = POST_STATS_NAMES[code]
+            if key not in self.post:
+                self.post[key] = self.make()
+            collect(self.post[key], code)
+
+    @staticmethod
+    def check(modes, discard_trimmed, discard_untrimmed, merging):
+        """Refuse post-trim statistics the reference cannot make, before any output is opened."""
+        if "post" not in modes:
+            return
+        if merging:
+            raise NotImplementedError("post-trim statistics of merged pairs (the reference collects them with "
+                                      "read2 = None and fails)")
+        if discard_trimmed or discard_untrimmed:
+            raise NotImplementedError("post-trim statistics with --discard-trimmed / --discard-untrimmed / "
+                                      "--untrimmed-output (the reference's trimmed / untrimmed filters have no name)")
+
+    def summary(self):
+        out = {}
+        if self.pre is not None:
+            out["pre"] = {0: self.pre.summarize()}
+        if self.post is not None:
+            out["post"] = {name: {0: st.summarize()} for name, st in self.post.items()}
+        return out
+
+
 def write_mask(batch, begin, end, ubegin, uend):
     """'N' over the masked parts [begin, ubegin) and [uend, end) of every sequence line of the chunk: after it the
     read IS what AdapterCutter's 'mask' action returns (modifiers.py:155-172), for the stages that look at bases."""
@@ -152,8 +218,13 @@ class TrimPipeline(object):
     def __init__(self, adapters=(), times=1, action="trim", cut=(), nextseq_trim=None, quality_cutoff=None,
                  quality_base=33, trim_n=False, minimum_length=None, maximum_length=None, max_n=None,
                  discard_trimmed=False, discard_untrimmed=False, op_order="CGQAW", aux=None, length_tag=None,
-                 strip_suffix=(), prefix="", suffix="", zero_cap=False, outputs=None, cut_min=(), bisulfite=None):
+                 strip_suffix=(), prefix="", suffix="", zero_cap=False, outputs=None, cut_min=(), bisulfite=None,
+                 stats=None):
         self.adapters = list(adapters)
+        # stats=("pre",) / ("post",) / ("pre", "post"): trim_file leaves the reference's --stats summary in
+        # self.stats_summary (TrimStats)
+        self.stats = _stats_modes(stats)
+        self._stats = None
         # --bisulfite: a list of cutters applied after the op-order stages and before --trim-n (trim/__init__.py:497-516):
         # ("min", front, back, count_trimmed, only_trimmed) = MinCutter, ("nondir", rrbs) = NonDirectionalBisulfiteTrimmer
         self.bisulfite = list(bisulfite or ())
@@ -371,6 +442,8 @@ class TrimPipeline(object):
 
     def run(self, batch):
         """All stages over one FastqBatch; returns a TrimResult."""
+        if self._stats is not None and self._stats.pre is not None:
+            self._stats.pre.collect_batch(batch)          # before any stage writes into the chunk
         n = len(batch)
         begin = torch.zeros((n,), dtype=torch.int32, device=batch.records.device)
         end = batch.seq_lens.clone()
@@ -478,6 +551,7 @@ class TrimPipeline(object):
         ``self.stage_seconds``."""
         import time
         from .fastq import ChunkedFastqReader, StageClock, make_sink
+        TrimStats.check(self.stats, self.discard_trimmed, self.discard_untrimmed, False)
         be = _lib.get_backend()
         totals = {name: 0 for name in DEST_NAMES.values()}
         clock = StageClock()
@@ -486,6 +560,7 @@ class TrimPipeline(object):
         aux_files = {kind: open_by_extension(path) for kind, path in (self.aux or {}).items()}
         dest_codes = {name: code for code, name in DEST_NAMES.items()}
         dest_files = {dest_codes[kind]: open_by_extension(path) for kind, path in self.outputs.items()}
+        self._stats = TrimStats(self.stats, False, self.quality_base) if self.stats else None
         try:
             while True:
                 batch = reader.next_batch()
@@ -495,6 +570,9 @@ class TrimPipeline(object):
                 text = be.fastq_emit(res.batch.data, res.batch.records, res.begin, res.end, res.ubegin, res.uend, res.dest,
                                      _lib.DEST_KEEP)
                 counts = res.counts()
+                if self._stats is not None:
+                    self._stats.add_post(counts, lambda st, code: st.collect_batch(
+                        res.batch, res.begin, res.end, res.ubegin, res.uend, res.dest, code))
                 clock.add("trim_and_format", t0)
                 sink.write(text)
                 if aux_files:                                 # host-assembled lines (debugging outputs, not a throughput path)
@@ -506,7 +584,10 @@ class TrimPipeline(object):
                     totals[name] += v
                 if done:
                     break
+            if self._stats is not None:
+                self.stats_summary = self._stats.summary()
         finally:
+            self._stats = None
             reader.close()
             sink.close()
             for fh in list(aux_files.values()) + list(dest_files.values()):
@@ -559,12 +640,17 @@ class PairedTrimPipeline(object):
     become ONE read -- destination ``DEST_MERGED``, text in ``PairedTrimResult.merged`` -- corrected
     first with ``correct_mismatches`` unless the insert aligner already saw the pair."""
 
+    stats, _stats = (), None                                              # (LegacyPairedPipeline skips __init__)
+
     def __init__(self, adapters1=(), adapters2=(), aligner="adapter", times=1, action="trim", cut=(), cut2=(),
                  nextseq_trim=None, quality_cutoff=None, quality_base=33, trim_n=False, minimum_length=None,
                  maximum_length=None, max_n=None, discard_trimmed=False, discard_untrimmed=False, pair_filter="any",
                  op_order="CGQAW", insert_args=None, correct_mismatches=None, merge_overlapping=False,
                  merge_min_overlap=0.9, merge_error_rate=0.2, aux=None, length_tag=None, strip_suffix=(), prefix="",
-                 suffix="", zero_cap=False, outputs=None, cut_min=(), cut_min2=(), bisulfite=None, bisulfite2=None):
+                 suffix="", zero_cap=False, outputs=None, cut_min=(), cut_min2=(), bisulfite=None, bisulfite2=None,
+                 stats=None):
+        self.stats = _stats_modes(stats)                                  # as TrimPipeline's: trim_files' summary
+        self._stats = None
         # {"too_short" | "too_long" | "untrimmed": (path for read 1, path for read 2)}: the filtered pairs' own files
         self.outputs = dict(outputs) if outputs else {}
         if "untrimmed" in self.outputs:
@@ -775,6 +861,8 @@ class PairedTrimPipeline(object):
     def run(self, batch1, batch2):
         if len(batch1) != len(batch2):
             raise ValueError("the two FASTQ batches hold different numbers of records")
+        if self._stats is not None and self._stats.pre is not None:
+            self._stats.pre.collect_batch(batch1, batch2)    # before any stage writes into the chunks
         be = batch1.backend
         n = len(batch1)
         dev = batch1.records.device
@@ -852,6 +940,7 @@ class PairedTrimPipeline(object):
         ``out1`` and part i of ``out2`` hold the same pairs in the same order."""
         import time
         from .fastq import ChunkedFastqReader, StageClock, make_sink
+        TrimStats.check(self.stats, self.p1.discard_trimmed, self.p1.discard_untrimmed, self.merge_overlapping)
         be = _lib.get_backend()
         totals = {name: 0 for name in DEST_NAMES.values()}
         clock = StageClock()
@@ -865,6 +954,7 @@ class PairedTrimPipeline(object):
             if merged_out is not None:
                 # a merged record is at most its two input records, and each input chunk may carry up to 64 MB over
                 sinks.append(make_sink(merged_out, output_parts, 2 * (chunk_bytes + (64 << 20)) + 32, be, clock, keep=keep_output))
+        self._stats = TrimStats(self.stats, True, self.p1.quality_base) if self.stats else None
         try:
             while True:
                 batches = [r.next_batch() for r in readers]
@@ -878,6 +968,11 @@ class PairedTrimPipeline(object):
                 texts = [be.fastq_emit(r.batch.data, r.batch.records, r.begin, r.end, r.ubegin, r.uend, r.dest,
                                        _lib.DEST_KEEP) for r in (res.read1, res.read2)]
                 counts = res.counts()
+                if self._stats is not None:
+                    r1, r2 = res.read1, res.read2
+                    self._stats.add_post(counts, lambda st, code: st.collect_batch(
+                        r1.batch, r2.batch, r1.begin, r1.end, r2.begin, r2.end, r1.ubegin, r1.uend, r2.ubegin, r2.uend,
+                        res.dest, code))
                 clock.add("trim_and_format", t0)
                 for k in range(2):
                     sinks[k].write(texts[k])
@@ -895,7 +990,10 @@ class PairedTrimPipeline(object):
                     break
                 if any(done):
                     raise ValueError("the two input files hold different numbers of records")
+            if self._stats is not None:
+                self.stats_summary = self._stats.summary()
         finally:
+            self._stats = None
             for obj in readers + sinks + list(aux_files.values()) + [fh for fhs in dest_files.values() for fh in fhs]:
                 obj.close()
             self.stage_seconds = dict(clock.seconds)

@@ -693,6 +693,42 @@ int atr_merge_emit_batch(const atr_result *d_align, const uint8_t *d_kind, const
                          int min_qual_difference, const uint8_t comp[256], const int64_t *d_offsets, int32_t *d_corrected,
                          int64_t *d_error, uint8_t *d_out, void *stream);
 
+
+/* Read statistics (ReadStatistics.collect_record, commands/stats.py:194-255; atropos qc, trim --stats, error
+ * -a quality) over a device-resident FASTQ chunk.  The statistics live in a caller-allocated block of uint64
+ * counters of atr_read_stats_bytes(max_len) bytes: the read count, the longest non-empty read, the number of
+ * non-empty reads with qualities, reads skipped because they were longer than `longest`; the length histogram
+ * (0 .. max_len), the GC% histogram (101 bins, round((C + G) * 100 / len) half to even), the mean-quality
+ * histogram (256 bins, bin = round(sum(q - quality_base) / len) + quality_base), per position below max_len
+ * counts of every sequence byte and every quality byte (rows of 256), and for every bin of the three histograms
+ * ~(stream index of the first read that landed in it) (0: none; the reference's histograms are dicts in first-seen
+ * order, which its median follows).  Counts are integers: the result does not depend on launch shape
+ * or on the order of calls.
+ *
+ * atr_read_stats_bytes: the block size, or ATR_ERR_INVALID (max_len < 1) / ATR_ERR_UNSUPPORTED (max_len >
+ * ATR_MAX_LONG_READ_LEN).  atr_read_stats_clear zeroes a block.
+ *
+ * atr_read_stats_batch adds the records of a chunk (atr_fastq_index) into the block, as atr_fastq_emit would
+ * write them: sequence[begin:end], the bases outside [unmasked_begin, unmasked_end) read as 'N'.  d_begin / d_end
+ * may be NULL (the whole sequence line), d_unmasked_begin / d_unmasked_end may be NULL (no mask; they need
+ * d_begin), d_dest may be NULL (every record; else only those with d_dest[r] == which).  Zero-length reads add
+ * to the count and the length histogram only; a record without a quality line (qual_len 0) adds no quality
+ * statistics.  longest: an upper bound of the kept lengths, at most max_len; a longer record is not collected
+ * but counted among the skipped ones.  quality_base in 0 .. 255.  index_base >= 0: stream index of the chunk's
+ * first record (record r is read index_base + r of the stream).
+ *
+ * atr_read_stats_merge: d_dst += d_src, both blocks laid out for their own max_len (dst_max_len >= src_max_len);
+ * d_src's reads follow d_dst's: its read indices are shifted by index_offset >= 0 (d_dst's number of reads).
+ * Argument errors are reported before anything is launched. */
+int64_t atr_read_stats_bytes(int max_len);
+int atr_read_stats_clear(void *d_stats, int max_len, void *stream);
+int atr_read_stats_batch(void *d_stats, int max_len, int longest, int quality_base, const uint8_t *d_bytes,
+                         const atr_fastq_record *d_records, const int32_t *d_begin, const int32_t *d_end,
+                         const int32_t *d_unmasked_begin, const int32_t *d_unmasked_end, const uint8_t *d_dest,
+                         int which, int64_t n, int64_t index_base, void *stream);
+int atr_read_stats_merge(void *d_dst, int dst_max_len, const void *d_src, int src_max_len, int64_t index_offset,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
