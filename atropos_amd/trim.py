@@ -1,4 +1,4 @@
-"""Device-resident single-end trimming pipeline: FASTQ bytes in, trimmed FASTQ bytes out.
+"""Device-resident trimming pipeline, single-end and paired-end: FASTQ bytes in, trimmed FASTQ bytes out.
 
 This is the batched, stage-wise replacement for the reference's per-read loop
 ``RecordHandler.handle_record`` -> ``Modifiers.modify`` -> ``Filters.filter`` ->
@@ -12,15 +12,20 @@ Stages, in the order the reference's ``op_order`` (default "CGQAW") and the fixe
   G  NextseqQualityTrimmer          -> atr_quality_trim_batch(nextseq=1)
   Q  QualityTrimmer                 -> atr_quality_trim_batch
   A  AdapterCutter(times, action)   -> atr_pack_records + atr_locate_batch + atr_adapter_postfilter
-                                       + atr_match_trim_batch per round
-  -  NEndTrimmer (--trim-n)         -> atr_nend_trim_batch
-  -  filters (-m, -M, --max-n, --discard-trimmed/-untrimmed) -> atr_read_filter_batch
+                                       + atr_match_trim_batch per round (plain or linked adapters)
+     InsertAdapterCutter (paired)   -> the insert aligner + atr_insert_plan_batch (with error correction)
+  -  bisulfite trimmers (--bisulfite), then NEndTrimmer (--trim-n), then MinCutter (--cut-min)
+                                    -> interval arithmetic; atr_nend_trim_batch
+  -  filters (-m, -M, --max-n, --discard-trimmed/-untrimmed) -> atr_read_filter_batch (+ atr_pair_filter_batch)
+  -  MergeOverlapping (-R, paired)  -> atr_locate_pairs_batch + atr_merge_plan_batch + atr_merge_emit_batch
+  -  ZeroCapper (-z) and the read-name modifiers (length tag, suffix removal, prefix / suffix)
   -  FastqFormat                    -> atr_fastq_emit
 
-What the pipeline does not do (it raises instead of silently differing): paired-end input,
-anchored adapters without indels, modifiers that rewrite names or bases (length tags,
-suffix removal, double encoding, zero cap, bisulfite trimmers, merging), info/rest files.
-Those stay on the per-read object path (``atropos_amd.modifiers``).
+Paired-end input runs in "both" mode (``PairedTrimPipeline``) or in the reference's legacy mode
+(``LegacyPairedPipeline``).  ``trim_file`` / ``trim_files`` also write the info / rest / wildcard files and the
+too-short / too-long / untrimmed outputs, and make the --stats pre / post summaries.  What the pipeline does not
+cover (options ``pipeline_from_args`` does not know, and the combinations the constructors refuse) raises instead
+of silently differing; those stay on the per-read object path (``atropos_amd.modifiers``).
 """
 import torch
 
@@ -119,6 +124,18 @@ def mask_before_later_stages(op_order, action):
     return action == "mask" and "A" in op_order and any(op in "GQ" for op in op_order[op_order.index("A") + 1:])
 
 
+def _raise_device_error(err):
+    """The exception the reference raises for the error word of the insert or merge kernels (pair * 8 + kind)."""
+    if err == _lib.INT64_MAX:
+        return
+    if err % 8 == 4:
+        raise ValueError("Invalid alignment while trying to merge pair %d" % (err // 8))
+    exc = {1: KeyError, 2: IndexError, 3: ValueError}[err % 8]
+    raise exc("error correction of pair %d: %s" % (err // 8, {
+        1: "base without a complement", 2: "overlap outside a read",
+        3: "Cannot determine the mode of an empty sequence"}[err % 8]))
+
+
 class TrimResult(object):
     """State of a batch after the pipeline: kept interval per read, the destination filter
     and the adapter flag; all device tensors."""
@@ -204,6 +221,125 @@ class TrimResult(object):
         return bytes(out.cpu().numpy().tobytes())
 
 
+class _Mate(object):
+    """The state of one read (of the pairs) during one ``run`` of ``pipe``: its chunk, the kept interval, the adapter
+    flag and the unmasked interval, and what the later stages and the result need of the adapter stage."""
+
+    def __init__(self, pipe, batch):
+        n = len(batch)
+        self.batch = batch
+        self.begin = torch.zeros((n,), dtype=torch.int32, device=batch.records.device)
+        self.end = batch.seq_lens.clone()
+        self.matched = torch.zeros((n,), dtype=torch.uint8, device=self.begin.device)
+        self.ubegin = self.uend = None
+        self.rounds = [] if pipe.aux else None                # the adapter rounds kept for the info / rest / wildcard files
+        self.sides = None                                     # per read: [any 5' match, any 3' match] (bisulfite)
+        self.after = None                                     # the interval right after the adapter stage (bisulfite)
+        self.last_which = (torch.zeros((n,), dtype=torch.int64, device=self.begin.device)
+                           if ("{name}" in pipe.prefix or "{name}" in pipe.suffix) else None)
+        self.unmasked = None                                  # a copy of the chunk before the mask / the zero cap
+
+
+def _run_stages(pipes, mates, insert_stage=None):
+    """The op-order stages, ``pipes[k]`` over ``mates[k]`` (one read, or the two reads of the pairs).  The A stage is
+    ``insert_stage()`` if given (the paired insert aligner), else the adapter stage of every pipe that has adapters;
+    returns what the last ``insert_stage()`` returned."""
+    op_order, action = pipes[0].op_order, pipes[0].action
+    found = None
+    for op in op_order:
+        if op != "A":
+            for pipe, m in zip(pipes, mates):
+                pipe._simple_stage(op, m)
+            continue
+        if insert_stage is not None:
+            found = insert_stage()
+        else:
+            for pipe, m in zip(pipes, mates):
+                if pipe.adapters:
+                    pipe._adapter_stage(m)
+        for m in mates:
+            if m.ubegin is not None and mask_before_later_stages(op_order, action):
+                if m.rounds is not None:                      # (the info / rest / wildcard lines show the read a match saw)
+                    m.unmasked = m.batch.data.clone()
+                write_mask(m.batch, m.begin, m.end, m.ubegin, m.uend)
+                m.ubegin = m.uend = None
+    return found
+
+
+def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out=None):
+    """The file loop of ``TrimPipeline.trim_file`` (one input) and ``PairedTrimPipeline.trim_files`` (two inputs in
+    lock step: the same number of records from each file per chunk); returns the destination counts."""
+    import time
+    from .fastq import ChunkedFastqReader, StageClock, make_sink
+    paired = len(paths_in) == 2
+    first = pipe.p1 if paired else pipe
+    merging = paired and pipe.merge_overlapping
+    TrimStats.check(pipe.stats, first.discard_trimmed, first.discard_untrimmed, merging)
+    be = _lib.get_backend()
+    totals = {name: 0 for name in DEST_NAMES.values()}
+    clock = StageClock()
+    readers = [ChunkedFastqReader(p, chunk_bytes, be, clock) for p in paths_in]
+    sinks = [make_sink(p, output_parts, chunk_bytes + (64 << 20) + 32, be, clock, keep=keep_output) for p in paths_out]
+    aux_files = {kind: open_by_extension(path) for kind, path in (pipe.aux or {}).items()}
+    dest_codes = {name: code for code, name in DEST_NAMES.items()}
+    dest_files = {dest_codes[kind]: [open_by_extension(p) for p in (paths if paired else (paths,))]
+                  for kind, paths in pipe.outputs.items()}               # (paired: a path per read)
+    if merging:
+        totals["merged"] = 0
+        if merged_out is not None:
+            # a merged record is at most its two input records, and each input chunk may carry up to 64 MB over
+            sinks.append(make_sink(merged_out, output_parts, 2 * (chunk_bytes + (64 << 20)) + 32, be, clock, keep=keep_output))
+    stats = TrimStats(pipe.stats, paired, first.quality_base) if pipe.stats else None
+    try:
+        while True:
+            batches = [r.next_batch() for r in readers]
+            if paired:
+                nrec = min(len(batches[0]), len(batches[1]))
+                heads = [batches[k].head(nrec) for k in range(2)]
+                done = [readers[k].advance(heads[k][1]) for k in range(2)]
+                if all(r.final for r in readers) and len(batches[0]) != len(batches[1]):
+                    raise ValueError("the two input files hold different numbers of records")
+                batches = [h[0] for h in heads]
+            else:
+                done = [readers[0].advance()]                 # starts reading the next chunk
+            t0 = time.perf_counter()
+            if stats is not None and stats.pre is not None:
+                stats.pre.collect_batch(*batches)             # before any stage writes into the chunks
+            res = pipe.run(*batches)
+            reads = (res.read1, res.read2) if paired else (res,)
+            texts = [be.fastq_emit(r.batch.data, r.batch.records, r.begin, r.end, r.ubegin, r.uend, r.dest,
+                                   _lib.DEST_KEEP) for r in reads]
+            counts = res.counts()
+            if stats is not None:                             # (collect_batch's order: batches, intervals, masks)
+                post =([r.batch for r in reads] + [t for r in reads for t in (r.begin, r.end)] +
+                        [t for r in reads for t in (r.ubegin, r.uend)] + [res.dest])
+                stats.add_post(counts, lambda st, code: st.collect_batch(*post, code))
+            clock.add("trim_and_format", t0)
+            for sink, text in zip(sinks, texts):
+                sink.write(text)
+            if len(sinks) == 3:
+                sinks[2].write(res.merged if res.merged is not None else texts[0][:0])
+            if aux_files:                                     # host-assembled lines (debugging outputs, not a throughput path)
+                for kind, blob in res.aux_text(tuple(aux_files)).items():
+                    aux_files[kind].write(blob)
+            for code, fhs in dest_files.items():              # the filtered reads that have a file of their own
+                for fh, r in zip(fhs, reads):
+                    fh.write(r.text(code))
+            for name, v in counts.items():
+                totals[name] += v
+            if all(done):
+                break
+            if any(done):
+                raise ValueError("the two input files hold different numbers of records")
+        if stats is not None:
+            pipe.stats_summary = stats.summary()
+    finally:
+        for obj in readers + sinks + list(aux_files.values()) + [fh for fhs in dest_files.values() for fh in fhs]:
+            obj.close()
+        pipe.stage_seconds = dict(clock.seconds)
+    return totals
+
+
 class TrimPipeline(object):
     """The single-end trimming steps of ``atropos trim`` as whole-batch device stages.
 
@@ -224,11 +360,9 @@ class TrimPipeline(object):
         # stats=("pre",) / ("post",) / ("pre", "post"): trim_file leaves the reference's --stats summary in
         # self.stats_summary (TrimStats)
         self.stats = _stats_modes(stats)
-        self._stats = None
         # --bisulfite: a list of cutters applied after the op-order stages and before --trim-n (trim/__init__.py:497-516):
         # ("min", front, back, count_trimmed, only_trimmed) = MinCutter, ("nondir", rrbs) = NonDirectionalBisulfiteTrimmer
         self.bisulfite = list(bisulfite or ())
-        self._sides = None                                                # per read: [any 5' match, any 3' match] (bisulfite)
         # --cut-min: MinCutter with its defaults (modifiers.py:587-650; after --trim-n, trim/__init__.py:520-524)
         cut_min = list(cut_min or ())
         self.min_front = sum(c for c in cut_min if c > 0)
@@ -245,9 +379,7 @@ class TrimPipeline(object):
         self.length_tag, self.strip_suffix = length_tag or None, list(strip_suffix or ())
         self.prefix, self.suffix, self.zero_cap = prefix or "", suffix or "", bool(zero_cap)
         self._name_mods = bool(self.length_tag or self.strip_suffix or self.prefix or self.suffix)
-        self._last_which = None
         self.aux = dict(aux) if aux else None            # {"info" | "rest" | "wildcard": path}: --info-file, --rest-file, --wildcard-file
-        self._rounds = None
         self.times, self.action = int(times), action
         if action not in ("trim", "mask", None):
             raise ValueError("action must be 'trim', 'mask' or None")
@@ -290,8 +422,9 @@ class TrimPipeline(object):
         flag = adapter._front_flag
         return 2 if flag is None else (1 if flag else 0)
 
-    def _round_plain(self, batch, begin, end, active, matched):
+    def _round_plain(self, m, active):
         """One ``_best_match`` + ``trimmed`` round (modifiers.py:107-122, :133-139)."""
+        batch, begin, end = m.batch, m.begin, m.end
         be = batch.backend
         source = RecordSource(batch, begin, end)
         best = which = None
@@ -307,66 +440,68 @@ class TrimPipeline(object):
         codes = torch.tensor([self._front_code(a) for a in self.adapters], dtype=torch.uint8, device=best.device)
         front = codes[which].contiguous() if len(self.adapters) > 1 else None
         took = (active != 0) & (best[:, 1] >= 0)                          # reads this round's match applies to
-        if self._rounds is not None:                                      # (... and the read the match saw)
-            self._rounds.append((took, best.clone(), which.clone(), begin.clone(), end.clone()))
-        if self._last_which is not None:
-            self._last_which = torch.where(took, which, self._last_which)
-        if self._sides is not None:                                       # Match.front / _guess_is_front of this round's match
+        if m.rounds is not None:                                          # (... and the read the match saw)
+            m.rounds.append((took, best.clone(), which.clone(), begin.clone(), end.clone()))
+        if m.last_which is not None:
+            m.last_which = torch.where(took, which, m.last_which)
+        if m.sides is not None:                                           # Match.front / _guess_is_front of this round's match
             code = codes[which]
             is_front = torch.where(code == 2, best[:, 2] == 0, code == 1)
-            self._sides[0] |= took & is_front
-            self._sides[1] |= took & ~is_front
-        be.match_trim_batch(best.contiguous(), front, int(codes[0].item()), begin, end, active, matched)
+            m.sides[0] |= took & is_front
+            m.sides[1] |= took & ~is_front
+        be.match_trim_batch(best.contiguous(), front, int(codes[0].item()), begin, end, active, m.matched)
 
-    def _round_linked(self, batch, begin, end, active, matched):
+    def _round_linked(self, m, active):
         """LinkedAdapter.match_to + trimmed (adapters/__init__.py:648-706) for linked adapters
         whose 5' parts are mutually exclusive: the first one whose 5' part matches is used."""
         from .adapters import linked_records_from_source
+        batch, begin, end = m.batch, m.begin, m.end
         be = batch.backend
         which, _count, front, back = linked_records_from_source(self.adapters, batch, begin, end, active)
         claimed = (which >= 0).to(torch.uint8)
         be.match_trim_batch(front.contiguous(), None, 1, begin, end, claimed.clone(), None)    # read[front.rstop:]
         be.match_trim_batch(back.contiguous(), None, 0, begin, end, claimed.clone(), None)     # then read[:back.rstart]
-        matched |= claimed
+        m.matched |= claimed
         active &= claimed                                                 # no 5' match: the loop over `times` stops
 
-    def _adapter_stage(self, batch, begin, end):
-        n = len(batch)
+    def _adapter_stage(self, m):
+        """Sets the mate's adapter flag and, with the 'mask' action, its unmasked interval."""
+        begin, end = m.begin, m.end
+        n = len(m.batch)
         dev = begin.device
-        matched = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        m.matched = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        m.ubegin = m.uend = None
         if not self.adapters or n == 0:
-            return matched, None, None
+            return
         before_b, before_e = begin.clone(), end.clone()
         if self.bisulfite:
-            self._sides = [torch.zeros((n,), dtype=torch.bool, device=dev), torch.zeros((n,), dtype=torch.bool, device=dev)]
+            m.sides = [torch.zeros((n,), dtype=torch.bool, device=dev), torch.zeros((n,), dtype=torch.bool, device=dev)]
         active = (end > begin).to(torch.uint8)                            # if len(read) == 0: return read
         for _ in range(self.times):
             if self._linked:
-                self._round_linked(batch, begin, end, active, matched)
+                self._round_linked(m, active)
             else:
-                self._round_plain(batch, begin, end, active, matched)
-        ubegin = uend = None
+                self._round_plain(m, active)
         if self.action == "mask":                                         # modifiers.py:155-172
-            ubegin, uend = begin.clone(), end.clone()
+            m.ubegin, m.uend = begin.clone(), end.clone()
             begin.copy_(before_b)
             end.copy_(before_e)
         elif self.action is None:                                         # :173-174
             begin.copy_(before_b)
             end.copy_(before_e)
-        if self.bisulfite:                                                # the interval right after the adapter stage
-            self._after = (begin.clone(), end.clone())
-        return matched, ubegin, uend
+        if self.bisulfite:
+            m.after = (begin.clone(), end.clone())
 
-    def _bisulfite_stage(self, batch, begin, end, matched):
+    def _bisulfite_stage(self, m):
         """MinCutter / RRBSTrimmer / NonDirectionalBisulfiteTrimmer (modifiers.py:587-650, :786-831) as interval
         arithmetic.  What a cutter counts as already trimmed: with count_trimmed everything that is gone from that end
         (Sequence.clipped + the matches' rsize_total = the interval); without, what the trimmers removed AFTER the
         adapter stage for a read with a match (clipped[2], clipped[3]) and everything for a read without one."""
-        has = matched != 0
+        batch, begin, end = m.batch, m.begin, m.end
+        has = m.matched != 0
         total = batch.seq_lens
-        after = getattr(self, "_after", None)
-        ab, ae = after if after is not None else (begin, end)
-        sides = self._sides if self._sides is not None else [torch.zeros_like(has), torch.zeros_like(has)]
+        ab, ae = m.after if m.after is not None else (begin, end)
+        sides = m.sides if m.sides is not None else [torch.zeros_like(has), torch.zeros_like(has)]
         for spec in self.bisulfite:
             if spec[0] == "nondir":
                 # ^C[AG]A on the read as it is now -> two bases off the 5' end (counting only what was cut after a
@@ -406,8 +541,9 @@ class TrimPipeline(object):
         end.copy_(ne)
 
     # ------------------------------------------------------------------ whole pipeline
-    def _simple_stage(self, op, batch, begin, end):
+    def _simple_stage(self, op, m):
         """The C, G, Q stages (interval updates without alignment)."""
+        batch, begin, end = m.batch, m.begin, m.end
         be = batch.backend
         if op == "C" and (self.cut_front or self.cut_back):
             be.clip_batch(batch.records, begin, end, self.cut_front, self.cut_back)
@@ -418,11 +554,13 @@ class TrimPipeline(object):
             be.quality_trim_batch(batch.data, batch.records, begin, end, int(self.quality_cutoff[0]),
                                   int(self.quality_cutoff[1]), self.quality_base, False)
 
-    def _filter_stage(self, batch, begin, end, ubegin, uend, matched, masks=False):
-        """--trim-n, then the read filters: destination byte per read (or the fail masks)."""
+    def _filter_stage(self, m, masks=False):
+        """The bisulfite cutters, --trim-n, --cut-min, then the read filters: destination byte per read (or the fail
+        masks)."""
+        batch, begin, end, ubegin, uend = m.batch, m.begin, m.end, m.ubegin, m.uend
         be = batch.backend
         if self.bisulfite:
-            self._bisulfite_stage(batch, begin, end, matched)
+            self._bisulfite_stage(m)
         if self.trim_n:
             be.nend_trim_batch(batch.data, batch.records, begin, end, ubegin, uend)
         if self.min_front or self.min_back:
@@ -437,49 +575,29 @@ class TrimPipeline(object):
         min_len = self.minimum_length if self.minimum_length is not None and self.minimum_length > 0 else 0
         max_len = self.maximum_length if self.maximum_length is not None else -1
         max_n = float(self.max_n) if self.max_n is not None else -1.0
-        return be.read_filter_batch(batch.data, batch.records, begin, end, ubegin, uend, matched, min_len, max_len,
+        return be.read_filter_batch(batch.data, batch.records, begin, end, ubegin, uend, m.matched, min_len, max_len,
                                     max_n, self.discard_trimmed, self.discard_untrimmed, masks=masks)
 
     def run(self, batch):
         """All stages over one FastqBatch; returns a TrimResult."""
-        if self._stats is not None and self._stats.pre is not None:
-            self._stats.pre.collect_batch(batch)          # before any stage writes into the chunk
-        n = len(batch)
-        begin = torch.zeros((n,), dtype=torch.int32, device=batch.records.device)
-        end = batch.seq_lens.clone()
-        matched = torch.zeros((n,), dtype=torch.uint8, device=begin.device)
-        ubegin = uend = None
-        self._rounds = [] if self.aux else None
-        self._sides = self._after = None
-        unmasked = None
-        self._last_which = (torch.zeros((n,), dtype=torch.int64, device=begin.device)
-                            if ("{name}" in self.prefix or "{name}" in self.suffix) else None)
-        for op in self.op_order:
-            if op == "A":
-                if self.adapters:
-                    matched, ubegin, uend = self._adapter_stage(batch, begin, end)
-                    if ubegin is not None and mask_before_later_stages(self.op_order, self.action):
-                        if self._rounds is not None:          # (the info / rest / wildcard lines show the read a match saw)
-                            unmasked = batch.data.clone()
-                        write_mask(batch, begin, end, ubegin, uend)
-                        ubegin = uend = None
-            else:
-                self._simple_stage(op, batch, begin, end)
-        dest = self._filter_stage(batch, begin, end, ubegin, uend, matched)
-        rounds, self._rounds = self._rounds, None
-        if self.zero_cap and n:
-            if rounds is not None and unmasked is None:            # a match's info record shows the read as the match saw it:
-                unmasked = batch.data.clone()                      # before ZeroCapper (align/__init__.py:145-170)
-            self._zero_cap(batch)
-        read_batch = batch if unmasked is None else FastqBatch(unmasked, batch.nbytes, batch.records, batch.backend,
-                                                               batch.line_ends)
-        if self._name_mods and n:
-            batch = self._rewrite_names(batch, begin, end, matched)
-        self._last_which = None
-        return TrimResult(batch, begin, end, ubegin, uend, matched, dest, rounds, self.adapters, read_batch)
+        m = _Mate(self, batch)
+        _run_stages([self], [m])
+        return self._result(m, self._filter_stage(m))
 
-    def _zero_cap(self, batch):
+    def _result(self, m, dest):
+        """The tail of a run: the zero cap and the read-name modifiers, then the TrimResult of the mate."""
+        b, n = m.batch, len(m.batch)
+        if self.zero_cap and n:
+            if m.rounds is not None and m.unmasked is None:        # a match's info record shows the read as the match saw it:
+                m.unmasked = b.data.clone()                        # before ZeroCapper (align/__init__.py:145-170)
+            self._zero_cap(m)
+        read_batch = b if m.unmasked is None else FastqBatch(m.unmasked, b.nbytes, b.records, b.backend, b.line_ends)
+        batch = self._rewrite_names(m) if self._name_mods and n else b
+        return TrimResult(batch, m.begin, m.end, m.ubegin, m.uend, m.matched, dest, m.rounds, self.adapters, read_batch)
+
+    def _zero_cap(self, m):
         """ZeroCapper (modifiers.py:709-720): quality characters below the base become the base, in the chunk."""
+        batch = m.batch
         rec = batch.records
         lens = rec[:, 5].to(torch.int64)
         start = rec[:, 4].to(torch.int64) & 0xFFFFFFFF
@@ -487,17 +605,18 @@ class TrimPipeline(object):
         idx = torch.repeat_interleave(start - first, lens) + torch.arange(int(lens.sum().item()), device=rec.device)
         batch.data[idx] = batch.data[idx].clamp(min=self.quality_base)
 
-    def _rewrite_names(self, batch, begin, end, matched):
+    def _rewrite_names(self, m):
         """LengthTagModifier, SuffixRemover, PrefixSuffixAdder (modifiers.py:652-695) in the reference's order: the
         new names are made on the host (string work per read, as in the reference), appended to the chunk in device
         memory, and the records point at them -- the formatter copies whatever name a record names."""
         import re
         import numpy as np
+        batch = m.batch
         raw = bytes(batch.data[:batch.nbytes].cpu().numpy().tobytes())
         recs = batch.records.cpu().numpy().astype("int64")
-        lens = (end - begin).clamp(min=0).cpu().tolist()
-        took = matched.cpu().tolist()
-        which = self._last_which.cpu().tolist() if self._last_which is not None else None
+        lens = (m.end - m.begin).clamp(min=0).cpu().tolist()
+        took = m.matched.cpu().tolist()
+        which = m.last_which.cpu().tolist() if m.last_which is not None else None
         tag = self.length_tag
         regex = re.compile(r"\b" + tag + r"[0-9]*\b") if tag else None
         names, offs, cur = [], [], 0
@@ -549,51 +668,7 @@ class TrimPipeline(object):
         part k mod N; what the reference's ``--no-writer-process`` does with its worker processes) -- for hosts
         that serialise the writers of one file.  The seconds the loop spent waiting per stage are left in
         ``self.stage_seconds``."""
-        import time
-        from .fastq import ChunkedFastqReader, StageClock, make_sink
-        TrimStats.check(self.stats, self.discard_trimmed, self.discard_untrimmed, False)
-        be = _lib.get_backend()
-        totals = {name: 0 for name in DEST_NAMES.values()}
-        clock = StageClock()
-        reader = ChunkedFastqReader(path_in, chunk_bytes, be, clock)
-        sink = make_sink(path_out, output_parts, chunk_bytes + (64 << 20) + 32, be, clock, keep=keep_output)
-        aux_files = {kind: open_by_extension(path) for kind, path in (self.aux or {}).items()}
-        dest_codes = {name: code for code, name in DEST_NAMES.items()}
-        dest_files = {dest_codes[kind]: open_by_extension(path) for kind, path in self.outputs.items()}
-        self._stats = TrimStats(self.stats, False, self.quality_base) if self.stats else None
-        try:
-            while True:
-                batch = reader.next_batch()
-                done = reader.advance()                       # starts reading the next chunk
-                t0 = time.perf_counter()
-                res = self.run(batch)
-                text = be.fastq_emit(res.batch.data, res.batch.records, res.begin, res.end, res.ubegin, res.uend, res.dest,
-                                     _lib.DEST_KEEP)
-                counts = res.counts()
-                if self._stats is not None:
-                    self._stats.add_post(counts, lambda st, code: st.collect_batch(
-                        res.batch, res.begin, res.end, res.ubegin, res.uend, res.dest, code))
-                clock.add("trim_and_format", t0)
-                sink.write(text)
-                if aux_files:                                 # host-assembled lines (debugging outputs, not a throughput path)
-                    for kind, blob in res.aux_text(tuple(aux_files)).items():
-                        aux_files[kind].write(blob)
-                for code, fh in dest_files.items():           # the filtered reads that have a file of their own
-                    fh.write(res.text(code))
-                for name, v in counts.items():
-                    totals[name] += v
-                if done:
-                    break
-            if self._stats is not None:
-                self.stats_summary = self._stats.summary()
-        finally:
-            self._stats = None
-            reader.close()
-            sink.close()
-            for fh in list(aux_files.values()) + list(dest_files.values()):
-                fh.close()
-            self.stage_seconds = dict(clock.seconds)
-        return totals
+        return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts)
 
 
 class PairedTrimResult(object):
@@ -640,8 +715,6 @@ class PairedTrimPipeline(object):
     become ONE read -- destination ``DEST_MERGED``, text in ``PairedTrimResult.merged`` -- corrected
     first with ``correct_mismatches`` unless the insert aligner already saw the pair."""
 
-    stats, _stats = (), None                                              # (LegacyPairedPipeline skips __init__)
-
     def __init__(self, adapters1=(), adapters2=(), aligner="adapter", times=1, action="trim", cut=(), cut2=(),
                  nextseq_trim=None, quality_cutoff=None, quality_base=33, trim_n=False, minimum_length=None,
                  maximum_length=None, max_n=None, discard_trimmed=False, discard_untrimmed=False, pair_filter="any",
@@ -650,7 +723,6 @@ class PairedTrimPipeline(object):
                  suffix="", zero_cap=False, outputs=None, cut_min=(), cut_min2=(), bisulfite=None, bisulfite2=None,
                  stats=None):
         self.stats = _stats_modes(stats)                                  # as TrimPipeline's: trim_files' summary
-        self._stats = None
         # {"too_short" | "too_long" | "untrimmed": (path for read 1, path for read 2)}: the filtered pairs' own files
         self.outputs = dict(outputs) if outputs else {}
         if "untrimmed" in self.outputs:
@@ -709,8 +781,10 @@ class PairedTrimPipeline(object):
         none[miss] = rec
         return none
 
-    def _insert_stage(self, b1, b2, st1, st2):
-        """InsertAdapterCutter over the batch (commands/trim/modifiers.py:391-496, no error correction)."""
+    def _insert_stage(self, mate1, mate2):
+        """InsertAdapterCutter over the batch (commands/trim/modifiers.py:391-496): sets the mates' adapter flags (and
+        unmasked intervals); returns (the pairs with an insert match, the pairs it corrected or None)."""
+        b1, b2, st1, st2 = mate1.batch, mate2.batch, (mate1.begin, mate1.end), (mate2.begin, mate2.end)
         be = b1.backend
         n = len(b1)
         src1, src2 = RecordSource(b1, st1[0], st1[1]), RecordSource(b2, st2[0], st2[1])
@@ -735,7 +809,7 @@ class PairedTrimPipeline(object):
             raise ValueError("%d second read(s) contain bases without an upper-case IUPAC code where they face the first "
                              "read; the device insert aligner cannot reverse-complement them" % bad)
         ins = self.insert.match_insert_batch(pb1, pb2).records
-        self._insert_matched = (ins[:, 0, 1] >= 0).to(torch.uint8)          # read.insert_overlap, modifiers.py:397
+        insert_matched = (ins[:, 0, 1] >= 0).to(torch.uint8)                # read.insert_overlap, modifiers.py:397
         # semi-global fallback (modifiers.py:405-407): only the pairs without an insert match need it
         miss = torch.nonzero(ins[:, 0, 1] < 0).squeeze(1)
         fb1 = self._fallback(self.p1.adapters[0], b1, st1, miss, n)
@@ -747,27 +821,25 @@ class PairedTrimPipeline(object):
         from .modifiers import COMP_TABLE, _ACTIONS
         correct = _ACTIONS[self.correct_mismatches] if self.correct_mismatches else -1
         # NB: with error correction the bases / qualities of both FASTQ chunks are rewritten in place
-        m1, m2, corrected, err = be.insert_plan_batch(
+        matched1, matched2, corrected, err = be.insert_plan_batch(
             ins.contiguous(), fb1.contiguous(), fb2.contiguous(), b1, b2, st1[0], st1[1], st2[0], st2[1], uend1, uend2,
             self.insert.min_insert_overlap, True, action, correct, 1, COMP_TABLE)
-        if err != _lib.INT64_MAX:                                          # the exception the reference raises
-            exc = {1: KeyError, 2: IndexError, 3: ValueError}[err % 8]
-            raise exc("error correction of pair %d: %s" % (err // 8, {
-                1: "base without a complement", 2: "overlap outside a read",
-                3: "Cannot determine the mode of an empty sequence"}[err % 8]))
-        self._already_corrected = None
-        if correct >= 0:
-            # read.corrected of both reads: a later correct_errors call (MergeOverlapping) returns at once for
-            # these pairs (modifiers.py:232-233) -- also for the ones corrected from complementary fallback
-            # matches, which have no insert match
-            self._already_corrected = (corrected.sum(dim=1) > 0).to(torch.uint8)
-            self.corrected_pairs += int(self._already_corrected.sum().item())
-            tot = corrected.sum(dim=0).cpu().tolist()
-            self.corrected_bp[0] += int(tot[0])
-            self.corrected_bp[1] += int(tot[1])
-        if action == 2:
-            return (m1, st1[0].clone(), uend1), (m2, st2[0].clone(), uend2)
-        return (m1, None, None), (m2, None, None)
+        _raise_device_error(err)
+        for m, matched, uend in ((mate1, matched1, uend1), (mate2, matched2, uend2)):
+            m.matched, m.ubegin, m.uend = matched, (m.begin.clone() if action == 2 else None), uend
+        # read.corrected of both reads: a later correct_errors call (MergeOverlapping) returns at once for these pairs
+        # (modifiers.py:232-233) -- also for the ones corrected from complementary fallback matches, which have no
+        # insert match
+        return insert_matched, (self._count_corrected(corrected) if correct >= 0 else None)
+
+    def _count_corrected(self, corrected):
+        """ErrorCorrectorMixin's counters over the changed-base counts of a batch; returns the pairs with a change."""
+        pairs = (corrected.sum(dim=1) > 0).to(torch.uint8)
+        self.corrected_pairs += int(pairs.sum().item())
+        tot = corrected.sum(dim=0).cpu().tolist()
+        self.corrected_bp[0] += int(tot[0])
+        self.corrected_bp[1] += int(tot[1])
+        return pairs
 
     def _merge_stage(self, b1, b2, st1, st2, insert_matched, already_corrected=None):
         """MergeOverlapping over the batch: the alignments ``Aligner(reverse_complement(read2), error_rate,
@@ -842,95 +914,35 @@ class PairedTrimPipeline(object):
         kind, text, corrected, err = be.merge_batch(align.contiguous(), need.to(torch.int32).contiguous(),
                                                     no_correct.contiguous(), b1, b2, st1[0], st1[1], st2[0], st2[1],
                                                     correct, 1, COMP_TABLE)
-        if err != _lib.INT64_MAX:
-            if err % 8 == 4:
-                raise ValueError("Invalid alignment while trying to merge pair %d" % (err // 8))
-            exc = {1: KeyError, 2: IndexError, 3: ValueError}[err % 8]
-            raise exc("error correction of pair %d: %s" % (err // 8, {
-                1: "base without a complement", 2: "overlap outside a read",
-                3: "Cannot determine the mode of an empty sequence"}[err % 8]))
+        _raise_device_error(err)
         merged = kind != 0
         if correct >= 0:
-            self.corrected_pairs += int((corrected.sum(dim=1) > 0).sum().item())
-            tot = corrected.sum(dim=0).cpu().tolist()
-            self.corrected_bp[0] += int(tot[0])
-            self.corrected_bp[1] += int(tot[1])
+            self._count_corrected(corrected)
         self.merged_pairs += int(merged.sum().item())
         return merged, text
 
     def run(self, batch1, batch2):
         if len(batch1) != len(batch2):
             raise ValueError("the two FASTQ batches hold different numbers of records")
-        if self._stats is not None and self._stats.pre is not None:
-            self._stats.pre.collect_batch(batch1, batch2)    # before any stage writes into the chunks
-        be = batch1.backend
-        n = len(batch1)
-        dev = batch1.records.device
-        st = []
-        for b in (batch1, batch2):
-            st.append([torch.zeros((n,), dtype=torch.int32, device=dev), b.seq_lens.clone()])
-        extra = [(torch.zeros((n,), dtype=torch.uint8, device=dev), None, None) for _ in range(2)]
-        pipes, batches = (self.p1, self.p2), [batch1, batch2]
-        insert_matched = already_corrected = None
-        unmasked = [None, None]
-        for pipe in pipes:
-            pipe._sides = pipe._after = None
-            pipe._rounds = [] if self.aux else None
-            pipe._last_which = (torch.zeros((n,), dtype=torch.int64, device=dev)
-                                if ("{name}" in pipe.prefix or "{name}" in pipe.suffix) else None)
-        for op in self.op_order:
-            if op == "A":
-                if self.aligner == "insert":
-                    extra = list(self._insert_stage(batch1, batch2, st[0], st[1]))
-                    insert_matched, already_corrected = self._insert_matched, self._already_corrected
-                else:
-                    for k in range(2):
-                        if pipes[k].adapters:
-                            extra[k] = pipes[k]._adapter_stage(batches[k], st[k][0], st[k][1])
-                for k in range(2):
-                    if extra[k][1] is not None and mask_before_later_stages(self.op_order, self.action):
-                        if pipes[k]._rounds is not None:
-                            unmasked[k] = batches[k].data.clone()
-                        write_mask(batches[k], st[k][0], st[k][1], extra[k][1], extra[k][2])
-                        extra[k] = (extra[k][0], None, None)
-            else:
-                for k in range(2):
-                    pipes[k]._simple_stage(op, batches[k], st[k][0], st[k][1])
-        masks = []
-        for k in range(2):
-            matched, ub, ue = extra[k]
-            masks.append(pipes[k]._filter_stage(batches[k], st[k][0], st[k][1], ub, ue, matched, masks=True))
-        dest = be.pair_filter_batch(masks[0], masks[1], self.min_affected)
+        pipes, mates = (self.p1, self.p2), (_Mate(self.p1, batch1), _Mate(self.p2, batch2))
+        insert = (lambda: self._insert_stage(*mates)) if self.aligner == "insert" else None
+        insert_matched, already_corrected = _run_stages(pipes, mates, insert) or (None, None)
+        masks = [pipe._filter_stage(m, masks=True) for pipe, m in zip(pipes, mates)]
+        dest = batch1.backend.pair_filter_batch(masks[0], masks[1], self.min_affected)
         merged_text = None
         if self.merge_overlapping:                                  # the last modifier, the first filter
             if self.action == "mask":
                 # masked adapters: MergeOverlapping sees the reads with their N's (modifiers.py:155-172 made them part of
                 # the sequence): written into the chunk here, the intervals then need no mask any more
-                for k in range(2):
-                    matched, ub, ue = extra[k]
-                    if ub is not None:
-                        self._write_mask(batches[k], st[k][0], st[k][1], ub, ue)
-                        extra[k] = (matched, None, None)
-            merged, merged_text = self._merge_stage(batch1, batch2, st[0], st[1], insert_matched, already_corrected)
+                for m in mates:
+                    if m.ubegin is not None:
+                        write_mask(m.batch, m.begin, m.end, m.ubegin, m.uend)
+                        m.ubegin = m.uend = None
+            m1, m2 = mates
+            merged, merged_text = self._merge_stage(batch1, batch2, (m1.begin, m1.end), (m2.begin, m2.end), insert_matched,
+                                                    already_corrected)
             dest = torch.where(merged, torch.full_like(dest, DEST_MERGED), dest)
-        res = []
-        for k in range(2):
-            pipe, read_batch = pipes[k], batches[k]
-            rounds, pipe._rounds = pipe._rounds, None
-            if pipe.zero_cap and n and rounds is not None and unmasked[k] is None:
-                unmasked[k] = batches[k].data.clone()              # (the info records of matched reads: before ZeroCapper)
-            if unmasked[k] is not None:
-                read_batch = FastqBatch(unmasked[k], read_batch.nbytes, read_batch.records, read_batch.backend, read_batch.line_ends)
-            if pipe.zero_cap and n:
-                pipe._zero_cap(batches[k])
-            if pipe._name_mods and n:
-                batches[k] = pipe._rewrite_names(batches[k], st[k][0], st[k][1], extra[k][0])
-            pipe._last_which = None
-            res.append(TrimResult(batches[k], st[k][0], st[k][1], extra[k][1], extra[k][2], extra[k][0], dest, rounds,
-                                  pipe.adapters, read_batch))
-        return PairedTrimResult(res[0], res[1], merged_text)
-
-    _write_mask = staticmethod(lambda batch, begin, end, ubegin, uend: write_mask(batch, begin, end, ubegin, uend))
+        return PairedTrimResult(self.p1._result(mates[0], dest), self.p2._result(mates[1], dest), merged_text)
 
     def trim_files(self, in1, in2, out1, out2, chunk_bytes=128 << 20, merged_out=None, keep_output=False, output_parts=1):
         """Stream two FASTQ files through the GPU in lock step (chunks of whole records, the
@@ -938,66 +950,7 @@ class PairedTrimPipeline(object):
         --merged-output file (without it merged reads are dropped, as by the reference).
         ``output_parts`` > 1: every output as that many part files (``TrimPipeline.trim_file``); part i of
         ``out1`` and part i of ``out2`` hold the same pairs in the same order."""
-        import time
-        from .fastq import ChunkedFastqReader, StageClock, make_sink
-        TrimStats.check(self.stats, self.p1.discard_trimmed, self.p1.discard_untrimmed, self.merge_overlapping)
-        be = _lib.get_backend()
-        totals = {name: 0 for name in DEST_NAMES.values()}
-        clock = StageClock()
-        readers = [ChunkedFastqReader(p, chunk_bytes, be, clock) for p in (in1, in2)]
-        sinks = [make_sink(p, output_parts, chunk_bytes + (64 << 20) + 32, be, clock, keep=keep_output) for p in (out1, out2)]
-        aux_files = {kind: open_by_extension(path) for kind, path in (self.aux or {}).items()}
-        dest_codes = {name: code for code, name in DEST_NAMES.items()}
-        dest_files = {dest_codes[kind]: [open_by_extension(p) for p in paths] for kind, paths in self.outputs.items()}
-        if self.merge_overlapping:
-            totals["merged"] = 0
-            if merged_out is not None:
-                # a merged record is at most its two input records, and each input chunk may carry up to 64 MB over
-                sinks.append(make_sink(merged_out, output_parts, 2 * (chunk_bytes + (64 << 20)) + 32, be, clock, keep=keep_output))
-        self._stats = TrimStats(self.stats, True, self.p1.quality_base) if self.stats else None
-        try:
-            while True:
-                batches = [r.next_batch() for r in readers]
-                nrec = min(len(batches[0]), len(batches[1]))
-                heads = [batches[k].head(nrec) for k in range(2)]
-                done = [readers[k].advance(heads[k][1]) for k in range(2)]
-                if all(r.final for r in readers) and len(batches[0]) != len(batches[1]):
-                    raise ValueError("the two input files hold different numbers of records")
-                t0 = time.perf_counter()
-                res = self.run(heads[0][0], heads[1][0])
-                texts = [be.fastq_emit(r.batch.data, r.batch.records, r.begin, r.end, r.ubegin, r.uend, r.dest,
-                                       _lib.DEST_KEEP) for r in (res.read1, res.read2)]
-                counts = res.counts()
-                if self._stats is not None:
-                    r1, r2 = res.read1, res.read2
-                    self._stats.add_post(counts, lambda st, code: st.collect_batch(
-                        r1.batch, r2.batch, r1.begin, r1.end, r2.begin, r2.end, r1.ubegin, r1.uend, r2.ubegin, r2.uend,
-                        res.dest, code))
-                clock.add("trim_and_format", t0)
-                for k in range(2):
-                    sinks[k].write(texts[k])
-                if len(sinks) == 3:
-                    sinks[2].write(res.merged if res.merged is not None else texts[0][:0])
-                if aux_files:
-                    for kind, blob in res.aux_text(tuple(aux_files)).items():
-                        aux_files[kind].write(blob)
-                for code, fhs in dest_files.items():
-                    for fh, text in zip(fhs, res.text(code)):
-                        fh.write(text)
-                for name, v in counts.items():
-                    totals[name] += v
-                if all(done):
-                    break
-                if any(done):
-                    raise ValueError("the two input files hold different numbers of records")
-            if self._stats is not None:
-                self.stats_summary = self._stats.summary()
-        finally:
-            self._stats = None
-            for obj in readers + sinks + list(aux_files.values()) + [fh for fhs in dest_files.values() for fh in fhs]:
-                obj.close()
-            self.stage_seconds = dict(clock.seconds)
-        return totals
+        return _trim_stream(self, [in1, in2], [out1, out2], chunk_bytes, keep_output, output_parts, merged_out)
 
     def trim_bytes(self, data1, data2, which=_lib.DEST_KEEP):
         """Two FASTQ texts in (same number of records), the two trimmed texts out."""
@@ -1013,9 +966,8 @@ class LegacyPairedPipeline(PairedTrimPipeline):
     filters.py:100-107), read 2 written as it came for every pair that is kept."""
 
     def __init__(self, first):
-        self.first = first
-        self.merge_overlapping, self.aux, self.outputs = False, None, {}
-        self.p1 = first
+        self.first = self.p1 = first                                      # (trim_files reads p1's filter settings)
+        self.stats, self.aux, self.outputs, self.merge_overlapping = (), None, {}, False
 
     def run(self, batch1, batch2):
         if len(batch1) != len(batch2):
