@@ -3,9 +3,16 @@
 
     python bench.py --gpus 1 --steps 20 --warmup 3                 # C2, the headline (BASELINE.json configs[1])
     python bench.py --config C3|C4|C5 ...                          # the other BASELINE configs, one GPU shard each
+    python bench.py --full ...                                     # + C3 / C4 / C5, CPU baselines, side figures, PMC traffic
     python bench.py --gpus N ...                                   # launches its own N ranks (one process per GPU)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # the same ranks under torchrun
     python bench.py --gpus N --single-process                      # the same shards from one process (threads + streams)
+
+A plain run does what its headline figure needs and nothing else: it builds one config's workload, warms up, times
+the steps, writes --dump-outputs and prints the line (with the default config, --dump-outputs also runs the steps of
+C3 / C4 / C5 to write their outputs; the line stays C2's).  --full adds everything else this script measures: with the
+default config the other BASELINE configs on the same clock (under "configs"), and at N = 1 each config's CPU baseline,
+its side measurements ("secondary") and the HBM traffic of its kernels from rocprofv3 PMC passes of this invocation.
 
 The ranks of a multi-GPU run meet only at a barrier and for the max-over-ranks of the elapsed time; both go over a
 gloo (host) process group -- the path has no exchange step, so there is no RCCL anywhere.
@@ -204,7 +211,7 @@ class C2(object):
             wb = synth.workload("C2", (rank + b * max(1, args.gpus)) * self.n, self.n, device=dev)
             self.batches.append(self.al.pack(wb["reads"], layout=self.batch.layout))
             del wb
-        self.sample = self.ascii[:min(self.n, 2_000_000)].cpu().numpy() if rank == 0 else None
+        self.sample = self.ascii[:min(self.n, 2_000_000)].cpu().numpy() if rank == 0 and not args.no_cpu_baseline else None
         self.filtered = not args.full_sweep
         if not args.secondary:
             self.ascii = None
@@ -420,7 +427,7 @@ class C3(object):
         chunk = 2_000_000
         for lo in range(0, self.n, chunk):
             w = synth.workload(self.name, rank * self.n + lo, min(chunk, self.n - lo), device=dev)
-            if self.sample is None and rank == 0:
+            if self.sample is None and rank == 0 and not args.no_cpu_baseline:
                 k = 200_000
                 self.sample = (w["reads1"][:k].cpu().numpy(), w["reads2"][:k].cpu().numpy())
             p1.append(w["reads1"])
@@ -489,7 +496,7 @@ class C5(C3):
         self.sample = None
         for b in range(self.nbatches):
             w = synth.workload("C5", (rank * self.nbatches + b) * self.n, self.n, device=dev)
-            if self.sample is None and rank == 0:
+            if self.sample is None and rank == 0 and not args.no_cpu_baseline:
                 k = 100_000
                 self.sample = tuple(w[key][:k].cpu().numpy() for key in ("reads1", "reads2", "quals1", "quals2"))
             self.batches.append(dict(b1=self.ia.pack(w["reads1"]), b2=self.ia.pack(w["reads2"], check=True),
@@ -561,7 +568,7 @@ class C4(object):
             chunks.append(w["reads"])
         self.w = w
         reads = upper_ascii(torch.cat(chunks))
-        self.sample = reads[:min(self.n, 1_000_000)].cpu().numpy() if rank == 0 else None
+        self.sample = reads[:min(self.n, 1_000_000)].cpu().numpy() if rank == 0 and not args.no_cpu_baseline else None
         linked = [LinkedAdapter(f, b, front_anchored=True, back_anchored=False, max_error_rate=w["max_error_rate"],
                                 min_overlap=w["min_overlap"], indel_cost=w["indel_cost"])
                   for f, b in zip(w["fronts"], w["backs"])]
@@ -984,14 +991,18 @@ def main():
     ap.add_argument("--rotate", type=int, default=3, help="C2: resident batches the timed steps rotate over (default 3)")
     ap.add_argument("--reads", type=int, default=None, help="reads (C2, C4) or pairs (C3, C5) per GPU and step of the "
                                                             "headline config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline figure too: C3 / C4 / C5 after C2 (default config), and at "
+                         "N = 1 the CPU baselines, the side measurements and roofline.traffic from rocprofv3 PMC passes of "
+                         "this invocation.  Without it: the steps of one config, roofline.traffic from the committed profile")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baselines")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="skip the pack-inclusive / ragged-batch / small-batch side measurements")
+                    help="--full: skip the pack-inclusive / ragged-batch / small-batch side measurements")
     ap.add_argument("--no-live-counters", dest="live_counters", action="store_false",
-                    help="take roofline.traffic from the committed profile instead of measuring it with rocprofv3 PMC passes "
-                         "of this invocation")
+                    help="--full: take roofline.traffic from the committed profile instead of measuring it with rocprofv3 PMC "
+                         "passes of this invocation")
     ap.add_argument("--no-other-configs", dest="others", action="store_false",
-                    help="default run: C2 only, without the C3 / C4 / C5 entries")
+                    help="--full: C2 only, without the C3 / C4 / C5 entries")
     ap.add_argument("--single-process", action="store_true",
                     help="--gpus N from ONE process: a host thread, backend and stream per GPU (no torchrun / NCCL); times "
                          "the headline config only")
@@ -1010,10 +1021,14 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last one returned (rank 0's shard) as DIR/<config>_<name>.npy, "
                          "float32, at most 64 MB in all (a fixed sample of rows, the same for every array of a config, "
-                         "when a config's outputs do not fit in its share)")
+                         "when a config's outputs do not fit in its share).  With the default config the steps of C3 / C4 / "
+                         "C5 run too, to write theirs")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                                            # a plain run: the headline figure and nothing else
+        args.secondary = args.live_counters = False
+        args.no_cpu_baseline = True
 
     if args.scaling:
         raise SystemExit(scaling_curve(args))
@@ -1068,10 +1083,13 @@ def main():
     else:
         _lib.set_backend(_lib.HipBackend(local_rank))
     head = args.config or "C2"
-    with_others = args.config is None and args.others and not args.full_sweep
-    args.dump_configs = 4 if with_others else 1                  # configs that share the --dump-outputs budget
+    four = args.config is None and args.others and not args.full_sweep
+    args.dump_configs = 4 if four else 1                         # configs that share the --dump-outputs budget
+    # --full times C3 / C4 / C5 after C2 and reports them; a plain run with --dump-outputs runs their steps only to
+    # write their outputs, and its line stays C2's alone
+    with_others = four and (args.full or args.dump_outputs is not None)
     line = measure(CONFIGS[head], args, rank, world, local_rank, dist, True, defer_secondary=with_others)
-    if args.config is None and args.others and not args.full_sweep:
+    if with_others:
         # the other BASELINE configs on the same clock: same steps / warmup, one after the other, each with its
         # own roofline and (N = 1) cpu_baseline.  A failure there must not cost the headline its line.
         others = {}
@@ -1084,9 +1102,11 @@ def main():
                 if dist is not None:
                     raise                                         # the ranks would lose step with each other
                 res = {"error": "%s: %s" % (type(exc).__name__, exc)}
+                if not args.full:
+                    sys.stderr.write("bench.py: %s failed, its outputs are not written: %s\n" % (name, res["error"]))
             if rank == 0:
                 others[name] = res
-        if rank == 0:
+        if rank == 0 and args.full:
             line["configs"] = others
     if rank == 0 and line is not None and "_secondary_later" in line:
         cfg, kernel_ms = line.pop("_secondary_later")

@@ -186,9 +186,9 @@ def _check_bench_line(line, world):
 
 
 def test_bench_launches_its_own_ranks():
-    """`python bench.py --gpus 2 --steps S --warmup W` -- the driver's N = 1 command with N substituted and NO
+    """`python bench.py --gpus 2 --steps S --warmup W --full` -- the driver's N = 1 command with N substituted and NO
     launcher around it -- must produce the 2-rank line by itself (round-3 verdict: it exited 1)."""
-    line = _run_bench([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1"], {})
+    line = _run_bench([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], {})
     _check_bench_line(line, 2)
     assert "self-launch" in line["launcher"]
 
@@ -197,7 +197,7 @@ def test_bench_under_torch_distributed_run():
     """The driver's multi-GPU form: torch.distributed.run starts the ranks, bench.py reads RANK / WORLD_SIZE."""
     line = _run_bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-                       "--steps", "2", "--warmup", "1"], {})
+                       "--steps", "2", "--warmup", "1", "--full"], {})
     _check_bench_line(line, 2)
     assert "torch.distributed.run" in line["launcher"]
 
@@ -228,6 +228,32 @@ def test_bench_dump_outputs(tmp_path, oracle):
     exp = oracle.locate_many(w["adapter"], reads, np.full(n, 150, np.int32), w["max_error_rate"], 14, False, False,
                              w["min_overlap"], w["indel_cost"], 2)
     assert np.array_equal(a["C2_records.npy"][:, :6], exp)
+
+
+def test_bench_plain_run_reports_the_headline_only(tmp_path):
+    """A plain `bench.py --gpus 1 --steps S --warmup W` reports C2 and nothing else: the headline fields, no other
+    config, CPU baseline or side measurement; with --dump-outputs it writes the same files as a --full run."""
+    import glob
+    import numpy as np
+    runs = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-secondary", "--no-live-counters"])):
+        d = tmp_path / name
+        line = _run_bench([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+                           "--dump-outputs", str(d)] + extra, {})
+        runs[name] = (line, {os.path.basename(p): np.load(p) for p in glob.glob(str(d / "*.npy"))})
+    line, dump = runs["plain"]
+    assert line["metric"] == "reads/s (whole node) 150 bp SE adapter-align" and line["unit"] == "reads/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "int32"
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    units = line["config"]["reads_per_gpu"]
+    assert abs(line["value"] - units / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+    assert not {"configs", "cpu_baseline", "secondary"} & set(line)
+    assert list(line["configs_summary"]) == ["C2"]
+    full_line, full_dump = runs["full"]
+    assert sorted(full_line["configs"]) == ["C3", "C4", "C5"]
+    assert sorted(dump) == sorted(full_dump) and {k.split("_")[0] for k in dump} == {"C2", "C3", "C4", "C5"}
+    for k in dump:
+        assert np.array_equal(dump[k], full_dump[k]), k
 
 
 def test_bench_scaling_curve_one_invocation():

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=/tmp/kt_$$
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python bench.py --no-cpu-baseline --steps 10 --warmup 2 "$@" > $OUT.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python bench.py --full --no-cpu-baseline --steps 10 --warmup 2 "$@" > $OUT.log 2>&1
 python - $OUT <<'PY'
 import csv, glob, sys, os
 for f in glob.glob(os.path.join(sys.argv[1], "**", "*kernel_stats.csv"), recursive=True):
