@@ -29,7 +29,8 @@
  *   orc_quality_trim_index            atropos/commands/trim/_qualtrim.pyx:7-50  (quality_trim_index)
  *   orc_nextseq_trim_index            atropos/commands/trim/_qualtrim.pyx:53-84 (nextseq_trim_index)
  *   orc_n_end_trim                    atropos/commands/trim/modifiers.py:766-784 (NEndTrimmer: ^N+ / N+$, upper-case N only)
- *   orc_locate_many / orc_linked_many / orc_match_insert_many (threaded drivers) -- harness only, no reference twin
+ *   orc_locate_many / orc_locate_pairs_many / orc_linked_many / orc_match_insert_many (threaded drivers) -- harness
+ *                                     only, no reference twin
  *
  * The DP keeps the reference's exact evaluation order: one column of
  * (cost, matches, origin) cells, Ukkonen's `last` cut-off, tie order
@@ -490,6 +491,72 @@ int orc_locate_many(const char *ref, int m, double e, int flags, int wc_ref, int
     if (nthreads > 1) for (int t = 0; t < nthreads; ++t) pthread_join(th[t], 0);
     free(th); free(jobs);
     return 0;
+}
+
+/* ---- threaded batch driver with a reference per pair (harness only) ------ */
+
+typedef struct {
+    const char *refs; const int *rlens; int64_t rstride;
+    const char *queries; const int *qlens; int64_t qstride;
+    double e; int flags, wc_ref, wc_query, min_overlap, indel, revcomp_ref;
+    int64_t lo, hi; int *out;
+} pjob_t;
+
+static void *pjob_main(void *arg) {
+    pjob_t *jb = (pjob_t *)arg;
+    int maxm = 0;
+    for (int64_t r = jb->lo; r < jb->hi; ++r) if (jb->rlens[r] > maxm) maxm = jb->rlens[r];
+    char *rc = (char *)malloc((size_t)maxm + 1);
+    if (!rc) return (void *)1;
+    intptr_t bad = 0;
+    for (int64_t r = jb->lo; r < jb->hi; ++r) {
+        int *o = jb->out + 6 * r;
+        const char *ref = jb->refs + r * jb->rstride;
+        const int m = jb->rlens[r];
+        int got = 0;
+        if (jb->revcomp_ref) {
+            if (orc_reverse_complement(ref, m, rc) != 0) got = -3;
+            ref = rc;
+        }
+        if (got == 0)
+            got = orc_locate(ref, m, jb->queries + r * jb->qstride, jb->qlens[r], jb->e, jb->flags, jb->wc_ref,
+                             jb->wc_query, jb->min_overlap, jb->indel, o);
+        if (got != 1) { o[0] = o[2] = o[3] = o[4] = o[5] = 0; o[1] = -1; }   /* ref_stop = -1 <=> None */
+        if (got < 0) bad = got == -3 ? 3 : got == -2 ? 2 : 1;
+    }
+    free(rc);
+    return (void *)bad;
+}
+
+/* orc_locate(refs[r], queries[r]) for every row r: rows of `rstride` / `qstride` ASCII bytes, lengths per row; with
+ * revcomp_ref the reference row is reverse-complemented first (what MergeOverlapping passes: modifiers.py:864-931).
+ * out: npairs x 6 ints, out[1] == -1 marks None.  Returns 0, or 1 (allocation), 2 (empty alignment), 3 (a base
+ * without complement) from the last row that failed. */
+int orc_locate_pairs_many(const char *refs, const int *rlens, int64_t rstride, const char *queries, const int *qlens,
+                          int64_t qstride, int64_t npairs, double e, int flags, int wc_ref, int wc_query,
+                          int min_overlap, int indel_cost, int revcomp_ref, int *out, int nthreads) {
+    tables_init();
+    { char c; orc_reverse_complement("", 0, &c); }          /* the complement table, before the workers share it */
+    if (nthreads < 1) nthreads = 1;
+    pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * nthreads);
+    pjob_t *jobs = (pjob_t *)malloc(sizeof(pjob_t) * nthreads);
+    if (!th || !jobs) { free(th); free(jobs); return 1; }
+    const int64_t per = (npairs + nthreads - 1) / nthreads;
+    int bad = 0;
+    for (int t = 0; t < nthreads; ++t) {
+        pjob_t *jb = &jobs[t];
+        jb->refs = refs; jb->rlens = rlens; jb->rstride = rstride;
+        jb->queries = queries; jb->qlens = qlens; jb->qstride = qstride;
+        jb->e = e; jb->flags = flags; jb->wc_ref = wc_ref; jb->wc_query = wc_query;
+        jb->min_overlap = min_overlap; jb->indel = indel_cost; jb->revcomp_ref = revcomp_ref; jb->out = out;
+        jb->lo = per * t < npairs ? per * t : npairs;
+        jb->hi = per * (t + 1) < npairs ? per * (t + 1) : npairs;
+        if (nthreads == 1) { intptr_t rv = (intptr_t)pjob_main(jb); if (rv) bad = (int)rv; }
+        else pthread_create(&th[t], 0, pjob_main, jb);
+    }
+    if (nthreads > 1) for (int t = 0; t < nthreads; ++t) { void *rv = 0; pthread_join(th[t], &rv); if (rv) bad = (int)(intptr_t)rv; }
+    free(th); free(jobs);
+    return bad;
 }
 
 

@@ -68,6 +68,10 @@ def lib():
                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_void_p, C.c_int]
         L.orc_locate_many.restype = C.c_int
+        L.orc_locate_pairs_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p, C.c_int]
+        L.orc_locate_pairs_many.restype = C.c_int
         L.orc_match_to.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double, C.c_int, C.c_int,
                                    C.c_int, C.c_int, I6]
         L.orc_match_to.restype = C.c_int
@@ -274,6 +278,34 @@ def locate_many(ref, reads, lens, e, flags, wildcard_ref=False, wildcard_query=F
     rc = lib().orc_locate_many(r, len(r), e, flags, int(wildcard_ref), int(wildcard_query), min_overlap,
                                indel_cost, reads.ctypes.data, lens.ctypes.data, reads.shape[1],
                                reads.shape[0], out.ctypes.data, nthreads)
+    if rc != 0:
+        raise MemoryError
+    return out
+
+
+def locate_pairs_many(refs, ref_lens, queries, query_lens, e, flags, wildcard_ref=False, wildcard_query=False,
+                      min_overlap=1, indel_cost=1, revcomp_ref=False, nthreads=1):
+    """locate(refs[i], queries[i], ...) for every row i -- a reference per pair, reverse-complemented first with
+    revcomp_ref (what MergeOverlapping aligns).  refs / queries: uint8 numpy [n, stride] of ASCII, ref_lens /
+    query_lens: int32 [n].  Returns int32 [n, 6]; row[1] == -1 marks None.  Raises what locate() and
+    reverse_complement() raise."""
+    import numpy as np
+    refs = np.ascontiguousarray(refs, dtype=np.uint8)
+    queries = np.ascontiguousarray(queries, dtype=np.uint8)
+    ref_lens = np.ascontiguousarray(ref_lens, dtype=np.int32)
+    query_lens = np.ascontiguousarray(query_lens, dtype=np.int32)
+    n = refs.shape[0]
+    assert refs.ndim == 2 and queries.ndim == 2 and queries.shape[0] == n and ref_lens.shape == (n,) and query_lens.shape == (n,)
+    assert n == 0 or (0 <= int(ref_lens.min()) and int(ref_lens.max()) <= refs.shape[1])
+    assert n == 0 or (0 <= int(query_lens.min()) and int(query_lens.max()) <= queries.shape[1])
+    out = np.empty((n, 6), dtype=np.int32)
+    rc = lib().orc_locate_pairs_many(refs.ctypes.data, ref_lens.ctypes.data, refs.shape[1], queries.ctypes.data,
+                                     query_lens.ctypes.data, queries.shape[1], n, e, flags, int(wildcard_ref),
+                                     int(wildcard_query), min_overlap, indel_cost, int(revcomp_ref), out.ctypes.data, nthreads)
+    if rc == 3:
+        raise KeyError("base without complement")
+    if rc == 2:
+        raise AssertionError("empty alignment (_align.pyx:490)")
     if rc != 0:
         raise MemoryError
     return out

@@ -1,6 +1,8 @@
 """Shared case generators / checkers for the emulation (CPU) and GPU parity tests."""
 import json
+import os
 import random
+import time
 
 from .conftest import load_golden, tup
 
@@ -40,6 +42,153 @@ def planted_reads(rng, ref, count, max_len=200, fixed_len=None):
             q = (q + rseq(rng, fixed_len))[:fixed_len]
         reads.append(q[:max_len])
     return reads
+
+
+# ---- whole-set comparison with the oracle --------------------------------------------------------------------------
+
+ORACLE_CHUNK_READS = 2_500_000          # reads / pairs handed to the oracle per call: host memory stays near 1 GB
+ORACLE_CHUNK_PAIRS = 2_000_000
+ORACLE_SECONDS = {}                     # label -> seconds spent inside the oracle (printed; DESIGN.md section 6 quotes them)
+
+
+def oracle_threads():
+    return min(16, os.cpu_count() or 1)
+
+
+def _host(x, lo=None, hi=None):
+    """rows [lo, hi) of a torch tensor (any device) or numpy array as a C-contiguous numpy array"""
+    import numpy as np
+    if lo is not None:
+        x = x[lo:hi]
+    if hasattr(x, "cpu"):
+        x = x.cpu().numpy()
+    return np.ascontiguousarray(x)
+
+
+def _timed(label, fn, *args):
+    t0 = time.perf_counter()
+    out = fn(*args)
+    ORACLE_SECONDS[label] = ORACLE_SECONDS.get(label, 0.0) + time.perf_counter() - t0
+    return out
+
+
+def _report(label, nrec):
+    print("oracle[%s]: %d records, %.1f s in the oracle so far" % (label, nrec, ORACLE_SECONDS.get(label, 0.0)))
+
+
+def assert_records_equal(got, exp, label, reads=None, lens=None, base=0):
+    """got == exp, row for row, for two numpy arrays of one dtype and one shape ([n], [n, 6], [n, 3, 6], [n, width]); a row
+    is everything under one index of axis 0.  EVERY row is compared.  On a mismatch the message carries the number of
+    differing rows, the index of the first one (plus `base`, the row's position in the whole set), both sides' rows there
+    and at up to four more differing indices, and -- with `reads` ([n, stride] ASCII, numpy or torch; `lens` cuts the row) --
+    the text of the first differing read.  Returns the number of rows."""
+    import numpy as np
+    assert isinstance(got, np.ndarray) and isinstance(exp, np.ndarray), \
+        "%s: numpy arrays expected, got %s and %s" % (label, type(got).__name__, type(exp).__name__)
+    assert got.dtype == exp.dtype, "%s: dtype %s != %s" % (label, got.dtype, exp.dtype)
+    assert got.shape == exp.shape, "%s: shape %r != %r" % (label, got.shape, exp.shape)
+    assert got.ndim >= 1, "%s: no row axis" % label
+    n = got.shape[0]
+    assert reads is None or len(reads) == n, "%s: %d reads for %d rows" % (label, len(reads), n)
+    neq = got != exp
+    if neq.ndim > 1:
+        neq = neq.any(axis=tuple(range(1, neq.ndim)))
+    bad = np.flatnonzero(neq)
+    if len(bad) == 0:
+        return n
+    lines = ["%s: %d of %d rows differ, the first at %d" % (label, len(bad), n, base + int(bad[0]))]
+    for i in bad[:5]:
+        lines.append("  row %d: got %s  expected %s" % (base + int(i), got[i].tolist(), exp[i].tolist()))
+    if reads is not None:
+        i = int(bad[0])
+        row = _host(reads[i])
+        if lens is not None:
+            row = row[:int(lens[i])]
+        lines.append("  read %d: %s" % (base + i, bytes(row).decode("latin-1")))
+    raise AssertionError("\n".join(lines))
+
+
+def check_locate_all(oracle, rec, ref, reads, lens, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost, label):
+    """rec[:, :6] (device or host records of Aligner.locate_batch, one per row of `reads`) against oracle.locate_many on
+    every read, in chunks.  reads: [n, width] ASCII tensor; lens: int32 tensor or None (every read `width` long).  Returns
+    the number of reads the oracle finds the adapter in."""
+    import numpy as np
+    n, width = reads.shape[0], reads.shape[1]
+    assert rec.shape[0] == n
+    nfound = 0
+    for lo in range(0, n, ORACLE_CHUNK_READS):
+        hi = min(n, lo + ORACLE_CHUNK_READS)
+        rd = _host(reads, lo, hi)
+        ln = np.full(hi - lo, width, np.int32) if lens is None else _host(lens, lo, hi).astype(np.int32)
+        exp = _timed(label, oracle.locate_many, ref, rd, ln, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost,
+                     oracle_threads())
+        assert_records_equal(_host(rec, lo, hi)[:, :6].astype(np.int32), exp, label, rd, ln, lo)
+        nfound += int((exp[:, 1] >= 0).sum())
+    _report(label, n)
+    return nfound
+
+
+def check_linked_all(oracle, forms, fronts, backs, reads, lens, e, min_overlap, indel_cost, label):
+    """(which, count, front[:, :6], back[:, :6]) of every read against oracle.linked_many, in chunks, for each entry of
+    `forms` = [(name, which, count, front, back), ...] -- several pipelines' outputs for the same reads share one oracle
+    pass.  Returns the numbers of reads with a 5' match and with a 3' match, by the oracle."""
+    import numpy as np
+    n, width = reads.shape[0], reads.shape[1]
+    nfront = nback = 0
+    for lo in range(0, n, ORACLE_CHUNK_READS):
+        hi = min(n, lo + ORACLE_CHUNK_READS)
+        rd = _host(reads, lo, hi)
+        ln = np.full(hi - lo, width, np.int32) if lens is None else _host(lens, lo, hi).astype(np.int32)
+        ew, ef, eb = _timed(label, oracle.linked_many, fronts, backs, rd, ln, e, min_overlap, indel_cost, True, False,
+                            oracle_threads())
+        for name, which, count, front, back in forms:
+            assert which.shape[0] == n and count.shape[0] == n and front.shape[0] == n and back.shape[0] == n
+            tag = "%s %s" % (label, name)
+            assert_records_equal(_host(which, lo, hi).astype(np.int32), ew[:, 0].astype(np.int32), tag + " which", rd, ln, lo)
+            assert_records_equal(_host(count, lo, hi).astype(np.int32), ew[:, 1].astype(np.int32), tag + " count", rd, ln, lo)
+            assert_records_equal(_host(front, lo, hi)[:, :6].astype(np.int32), ef, tag + " front", rd, ln, lo)
+            assert_records_equal(_host(back, lo, hi)[:, :6].astype(np.int32), eb, tag + " back", rd, ln, lo)
+        nfront += int((ew[:, 0] >= 0).sum())
+        nback += int((eb[:, 1] >= 0).sum())
+    _report(label, n)
+    return nfront, nback
+
+
+def check_insert_all(oracle, orc, rec, reads1, reads2, label, base=0):
+    """rec[:, :, :6] (InsertAligner.match_insert_batch records, [n, 3, >= 6]) of every pair against
+    oracle.match_insert_many as int32 [n, 3, 6], in chunks; equal-length reads.  Returns the oracle's records."""
+    import numpy as np
+    n, width = reads1.shape[0], reads1.shape[1]
+    assert rec.shape[0] == n and reads2.shape == reads1.shape
+    out = []
+    for lo in range(0, n, ORACLE_CHUNK_PAIRS):
+        hi = min(n, lo + ORACLE_CHUNK_PAIRS)
+        r1, r2 = _host(reads1, lo, hi), _host(reads2, lo, hi)
+        ln = np.full(hi - lo, width, np.int32)
+        exp = _timed(label, oracle.match_insert_many, orc, r1, ln, r2, ln, oracle_threads())
+        assert_records_equal(_host(rec, lo, hi)[:, :, :6].astype(np.int32), exp, label, r1, ln, base + lo)
+        out.append(exp)
+    _report(label, n)
+    return out[0] if len(out) == 1 else np.concatenate(out)
+
+
+def check_pairs_all(oracle, rec, reads2, reads1, e, flags, label):
+    """rec[:, :6] (PairAligner(e, flags, revcomp_ref=True).locate_batch records; min_overlap 1, indel cost 1, no wildcards)
+    against oracle.locate_pairs_many -- reference = reverse complement of reads2's row, query = reads1's row -- on every
+    pair, in chunks; equal-length reads.  Returns the number of pairs compared."""
+    import numpy as np
+    n = reads1.shape[0]
+    assert rec.shape[0] == n and reads2.shape[0] == n
+    done = 0
+    for lo in range(0, n, ORACLE_CHUNK_PAIRS):
+        hi = min(n, lo + ORACLE_CHUNK_PAIRS)
+        r1, r2 = _host(reads1, lo, hi), _host(reads2, lo, hi)
+        l1, l2 = np.full(len(r1), r1.shape[1], np.int32), np.full(len(r2), r2.shape[1], np.int32)
+        exp = _timed(label, oracle.locate_pairs_many, r2, l2, r1, l1, e, flags, False, False, 1, 1, True, oracle_threads())
+        assert_records_equal(_host(rec, lo, hi)[:, :6].astype(np.int32), exp, label, r1, l1, lo)
+        done += len(r1)
+    _report(label, done)
+    return done
 
 
 def check_golden_locate(Aligner, unsupported_exc):
@@ -1532,11 +1681,11 @@ def check_long_reference(Aligner, oracle, AtroposHipError, batch_rounds=6):
     return done
 
 
-def check_ragged_tail_mode(Aligner, oracle, seed, nreads=20000, oracle_slice=1500):
+def check_ragged_tail_mode(Aligner, oracle, seed, nreads=20000):
     """Ragged batches at a size where the row-count bins fill whole waves (the window kernel's tail mode:
     columns counted from the read end): C2-like reads cut to random lengths -- including reads shorter than
     the adapter and empty ones -- for 3' adapters of several lengths and error rates; the filtered
-    pipeline against the full sweep on every read and against the oracle on a slice."""
+    pipeline against the full sweep and against the oracle (locate_many with the ragged lengths), all records."""
     import numpy as np
     import torch
     from atropos_amd import _lib, synth
@@ -1558,22 +1707,10 @@ def check_ragged_tail_mode(Aligner, oracle, seed, nreads=20000, oracle_slice=150
         got = al.locate_batch(rb).records.cpu()
         full = al.locate_batch(rb, filtered=False).records.cpu()
         assert torch.equal(got, full), (m, e, ic, flags, int((got != full).any(dim=1).sum()))
-        reads = w["reads"].numpy()
-        idx = [rng.randrange(nreads) for _ in range(oracle_slice)]
-        tuples = LocateTuples(got)
-        for i in idx:
-            q = bytes(reads[i, :int(lens[i])]).decode("ascii")
-            assert tuples[i] == oracle.locate(ref, q, e, flags, False, False, al.min_overlap, ic), (ref, q, e, flags)
+        check_locate_all(oracle, got, ref, w["reads"], lens, e, flags, False, False, al.min_overlap, ic,
+                         "ragged tail m=%d e=%g flags=%d" % (m, e, flags))
         total += nreads
     return total
-
-
-def LocateTuples(records):
-    """int16 [n, 8] records -> list of the reference's 6-tuples / None."""
-    out = []
-    for row in records.tolist():
-        out.append(None if row[1] < 0 else tuple(row[:6]))
-    return out
 
 
 def check_correct_errors_fixture():

@@ -148,7 +148,7 @@ def test_dpmatrix_debug(emu_backend):
 
 def test_ragged_tail_mode(emu_backend, oracle):
     from atropos_amd.align import Aligner
-    assert _cases.check_ragged_tail_mode(Aligner, oracle, 3, nreads=3000, oracle_slice=400) == 15000
+    assert _cases.check_ragged_tail_mode(Aligner, oracle, 3, nreads=3000) == 15000
 
 
 def test_pair_aligner_lds_column_fallback(emu_backend, oracle):

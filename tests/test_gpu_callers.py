@@ -36,10 +36,12 @@ def test_linked_sets_fused(hip_backend, oracle):
 
 def test_c4_shard_against_oracle(hip_backend, oracle):
     """BASELINE config C4, one GPU's shard in full (12.5 M x 150 bp, four linked adapters, e = 0.12):
-    a 250 k-read slice bit-exact against the oracle (LinkedAdapter.match_to = PREFIX match_to, then
-    BACK match_to on read[front.rstop:], adapters/__init__.py:671-690), the whole shard against the
-    step-wise device path (one kernel pipeline per adapter part, nothing shared with the fused
-    kernels but the DP cores), and size-independent properties of all 12.5 M record pairs."""
+    all records bit-exact against the oracle (LinkedAdapter.match_to = PREFIX match_to, then
+    BACK match_to on read[front.rstop:], adapters/__init__.py:671-690) -- the fused form and, against the
+    same oracle arrays, the grouped form (pack_groups / match_groups: what bench.py times for C4) -- the
+    whole shard against the step-wise device path (one kernel pipeline per adapter part, nothing shared
+    with the fused kernels but the DP cores), size-independent properties of all 12.5 M record pairs, and
+    all records of a 1 M-read ragged batch against the oracle."""
     import numpy as np
     import torch
     from atropos_amd import synth
@@ -56,17 +58,15 @@ def test_c4_shard_against_oracle(hip_backend, oracle):
     src = AsciiSource(reads)
     which, count, front, back = lset.match_source(src)
     torch.cuda.synchronize()
-    # (1) slice parity against the oracle
-    lo = 7_654_321
-    k = 250_000
-    sl = reads[lo:lo + k].cpu().numpy()
-    ew, ef, eb = oracle.linked_many(w["fronts"], w["backs"], sl, np.full(k, 150, np.int32), w["max_error_rate"],
-                                    w["min_overlap"], w["indel_cost"], True, False, 8)
-    assert np.array_equal(which[lo:lo + k].cpu().numpy(), ew[:, 0].astype(np.int32))
-    assert np.array_equal(count[lo:lo + k].cpu().numpy(), ew[:, 1].astype(np.int32))
-    assert np.array_equal(front[lo:lo + k, :6].cpu().numpy().astype(np.int32), ef)
-    assert np.array_equal(back[lo:lo + k, :6].cpu().numpy().astype(np.int32), eb)
-    assert (ew[:, 0] >= 0).mean() > 0.7 and (eb[:, 1] >= 0).mean() > 0.3
+    # (1) parity of all 12.5 M records against the oracle: the fused form and the grouped form, one oracle pass
+    assert lset.group_applies(reads.shape[1])
+    gw, gc, gf, gb = lset.match_groups(lset.pack_groups(reads, None))
+    torch.cuda.synchronize()
+    nfront, nback = _cases.check_linked_all(oracle, [("fused", which, count, front, back), ("grouped", gw, gc, gf, gb)],
+                                            w["fronts"], w["backs"], reads, None, w["max_error_rate"], w["min_overlap"],
+                                            w["indel_cost"], "C4 12.5 M")
+    assert nfront > 0.7 * n_total and nback > 0.3 * n_total
+    del gw, gc, gf, gb
     # (2) the whole shard against the step-wise device path
     w2, c2, f2, b2 = _linked_records_stepwise(las, src)
     assert torch.equal(which, w2) and torch.equal(count, c2)
@@ -92,25 +92,23 @@ def test_c4_shard_against_oracle(hip_backend, oracle):
     # (4) determinism, and independence of the batch split
     w3, c3, f3, b3 = lset.match_source(src)
     assert torch.equal(which, w3) and torch.equal(front, f3) and torch.equal(back, b3)
+    lo = 7_654_321
     part = lset.match_source(AsciiSource(reads[lo:lo + 100_037].contiguous()))
     assert torch.equal(part[0], which[lo:lo + 100_037]) and torch.equal(part[3], back[lo:lo + 100_037])
-    # (5) ragged lengths: the same reads cut to 60 .. 150 bases, a slice against the oracle
+    # (5) ragged lengths: the same reads cut to 60 .. 150 bases, all 1 M records against the oracle
     g = torch.Generator(device="cuda").manual_seed(11)
     lens = torch.randint(60, 151, (1_000_000,), generator=g, device="cuda", dtype=torch.int32)
     sub = reads[:1_000_000].contiguous()
     rw, rc, rf, rb = lset.match_source(AsciiSource(sub, lens))
-    ew, ef, eb = oracle.linked_many(w["fronts"], w["backs"], sub[:100_000].cpu().numpy(), lens[:100_000].cpu().numpy(),
-                                    w["max_error_rate"], w["min_overlap"], w["indel_cost"], True, False, 8)
-    assert np.array_equal(rw[:100_000].cpu().numpy(), ew[:, 0].astype(np.int32))
-    assert np.array_equal(rf[:100_000, :6].cpu().numpy().astype(np.int32), ef)
-    assert np.array_equal(rb[:100_000, :6].cpu().numpy().astype(np.int32), eb)
+    _cases.check_linked_all(oracle, [("fused", rw, rc, rf, rb)], w["fronts"], w["backs"], sub, lens, w["max_error_rate"],
+                            w["min_overlap"], w["indel_cost"], "C4 ragged 1 M")
 
 
 def test_linked_long_batches_mixed_sets(hip_backend, oracle):
     """Long batches (> 262 144 reads: per-block lists, offsets by atomics, one band launch, window launches by row class)
     of linked sets whose 3' aligners do NOT share a row class / indel mode -- a window launch per adapter, each reading
     its adapter's block of the set's device blob -- and of uniform sets of two and three adapters (one window launch):
-    a slice against the oracle, the whole batch against the same reads in short batches (the wavefront-per-read finish
+    all records against the oracle, the whole batch against the same reads in short batches (the wavefront-per-read finish
     or the window-word path: other kernels), equal-length and ragged."""
     import numpy as np
     import torch
@@ -145,16 +143,9 @@ def test_linked_long_batches_mixed_sets(hip_backend, oracle):
                 g = torch.Generator(device="cuda").manual_seed(5 + ci)
                 lens = torch.randint(50, 151, (n,), generator=g, device="cuda", dtype=torch.int32)
             which, count, front, back = lset.match_source(AsciiSource(reads, lens))
-            k = 60_000
-            lo = 123_457
-            ew, ef, eb = oracle.linked_many(fronts, backs, reads[lo:lo + k].cpu().numpy(),
-                                            np.full(k, 150, np.int32) if lens is None else lens[lo:lo + k].cpu().numpy(),
-                                            e, mo, indel, True, False, 8)
-            assert np.array_equal(which[lo:lo + k].cpu().numpy(), ew[:, 0].astype(np.int32)), (ci, ragged)
-            assert np.array_equal(count[lo:lo + k].cpu().numpy(), ew[:, 1].astype(np.int32)), (ci, ragged)
-            assert np.array_equal(front[lo:lo + k, :6].cpu().numpy().astype(np.int32), ef), (ci, ragged)
-            assert np.array_equal(back[lo:lo + k, :6].cpu().numpy().astype(np.int32), eb), (ci, ragged)
-            assert (eb[:, 1] >= 0).mean() > 0.05 and (ew[:, 0] >= 0).mean() > 0.5
+            nfront, nback = _cases.check_linked_all(oracle, [("fused", which, count, front, back)], fronts, backs, reads, lens,
+                                                    e, mo, indel, "mixed set %d%s" % (ci, " ragged" if ragged else ""))
+            assert nback > 0.05 * n and nfront > 0.5 * n
             for a in range(0, n, 100_000):
                 part = lset.match_source(AsciiSource(reads[a:a + 100_000].contiguous(), None if lens is None else lens[a:a + 100_000].contiguous()))
                 assert torch.equal(part[0], which[a:a + 100_000]) and torch.equal(part[1], count[a:a + 100_000]), (ci, ragged, a)
@@ -189,10 +180,10 @@ def test_long_multi_and_compare(hip_backend):
     assert _cases.check_long_multi_compare() == 36 * 8 + 30 * 5 + 60
 
 
-def _linked_group_check(oracle, reads, lens, fronts, backs, e, mo, ic, slice_lo, slice_k):
+def _linked_group_check(oracle, reads, lens, fronts, backs, e, mo, ic):
     """Grouped pipeline (5' parts at pack time, adapter-uniform plane64 sub-batches, the single-aligner two-pass pipeline
-    per 3' adapter) against the fused tile64 pipeline on every read and against the oracle on a slice; the slot-order
-    outputs against the batch-order ones."""
+    per 3' adapter) against the fused tile64 pipeline and against the oracle, all records; the slot-order outputs against
+    the batch-order ones."""
     import numpy as np
     import torch
     from atropos_amd.adapters import AsciiSource, LinkedAdapter, LinkedSet
@@ -231,19 +222,16 @@ def _linked_group_check(oracle, reads, lens, fronts, backs, e, mo, ic, slice_lo,
     bb = back[:, :6].cpu().numpy()[has]
     acc = bb[:, 1] >= 0
     assert np.array_equal(sb[acc], bb[acc])
-    # the oracle on a slice
-    k = min(slice_k, n - slice_lo)
-    sl = reads[slice_lo:slice_lo + k].cpu().numpy()
-    sl_lens = np.full(k, reads.shape[1], np.int32) if lens is None else lens[slice_lo:slice_lo + k].cpu().numpy().astype(np.int32)
-    ew, ef, eb = oracle.linked_many(fronts, backs, sl, sl_lens, e, mo, ic, True, False, 8)
-    assert np.array_equal(wh[slice_lo:slice_lo + k], ew[:, 0].astype(np.int32))
-    assert np.array_equal(front[slice_lo:slice_lo + k, :6].cpu().numpy().astype(np.int32), ef)
-    assert np.array_equal(back[slice_lo:slice_lo + k, :6].cpu().numpy().astype(np.int32), eb)
-    return int((wh >= 0).sum()), int((back[:, 1] >= 0).sum().item())
+    # the oracle on every read
+    nfront, nback = _cases.check_linked_all(oracle, [("grouped", which, count, front, back)], fronts, backs, reads, lens, e, mo, ic,
+                                            "linked groups n=%d nad=%d%s" % (n, len(fronts), "" if lens is None else " ragged"))
+    assert nfront == int((wh >= 0).sum()) and nback == int((back[:, 1] >= 0).sum().item())
+    return nfront, nback
 
 
 def test_linked_groups_c4(hip_backend, oracle):
-    """C4's reads through atr_linked_group_pack / atr_linked_group_match (round 6): 3 M reads equal-length, 1 M ragged."""
+    """C4's reads through atr_linked_group_pack / atr_linked_group_match (round 6): 3 M reads equal-length, 1 M ragged;
+    all records against the fused pipeline and against the oracle."""
     import torch
     from atropos_amd import synth
     from atropos_amd.adapters import upper_ascii
@@ -251,14 +239,14 @@ def test_linked_groups_c4(hip_backend, oracle):
     w = synth.workload("C4", 1_000_000, n, device="cuda")
     reads = upper_ascii(w["reads"])
     nf, nb = _linked_group_check(oracle, reads, None, w["fronts"], w["backs"], w["max_error_rate"], w["min_overlap"],
-                                 w["indel_cost"], 1_234_567, 150_000)
+                                 w["indel_cost"])
     assert nf > 0.7 * n and nb > 0.3 * n
     g = torch.Generator(device="cuda").manual_seed(11)
     sub = reads[:1_000_000].contiguous()
     lens = torch.randint(0, 151, (sub.shape[0],), generator=g, device="cuda", dtype=torch.int32)
     lens = torch.where(torch.rand(sub.shape[0], generator=g, device="cuda") < 0.7, torch.full_like(lens, 150), lens)
     nf, nb = _linked_group_check(oracle, sub, lens, w["fronts"], w["backs"], w["max_error_rate"], w["min_overlap"],
-                                 w["indel_cost"], 500_000, 100_000)
+                                 w["indel_cost"])
     assert nf > 0.5 * sub.shape[0]
 
 
@@ -280,6 +268,6 @@ def test_linked_groups_small_and_odd(hip_backend, oracle):
         lens = None
         if n % 2 == 1 and n > 100:
             lens = torch.from_numpy(rng.integers(0, 151, n).astype(np.int32)).cuda()
-        nf, _ = _linked_group_check(oracle, reads, lens, fronts, backs, 0.12, 3, 1, 0, min(n, 50_000))
+        nf, _ = _linked_group_check(oracle, reads, lens, fronts, backs, 0.12, 3, 1)
         total += nf
     assert total > 100_000

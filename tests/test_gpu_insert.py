@@ -43,8 +43,10 @@ def _rows(t):
 @pytest.mark.parametrize("name,count", [("C3", 10_000_000), ("C5", 2_000_000)])
 def test_full_size_insert(hip_backend, oracle, name, count):
     """BASELINE configs C3 (10 M x 2x150) / a 2 M-pair shard of C5 (2x250, read
-    wildcards) on the device: a slice bit-exact against the oracle plus
-    size-independent properties of every record."""
+    wildcards) on the device: all records of every chunk bit-exact against the oracle
+    (match_insert_many, int32 [n, 3, 6]), the results() objects of the first few
+    thousand pairs against the oracle pair by pair, plus size-independent properties
+    of every record."""
     from atropos_amd import synth
     from atropos_amd.align import InsertAligner
     kw = dict(read_wildcards=True) if name == "C5" else {}
@@ -81,7 +83,10 @@ def test_full_size_insert(hip_backend, oracle, name, count):
         assert torch.equal(rec, ia.match_insert_batch(b1, b2).records)
         part = ia.match_insert_batch(w["reads1"][1000:1000 + 70_001], w["reads2"][1000:1000 + 70_001]).records
         assert torch.equal(part, rec[1000:1000 + 70_001])
+        exp = _cases.check_insert_all(oracle, orc, rec, w["reads1"], w["reads2"], "%s insert" % name, lo)
+        assert int((exp[:, 0, 1] >= 0).sum()) == int(found.sum().item())
         if lo == 0:
+            # the object path (the only at-size check of results()): pair by pair on the head of the first chunk
             k = 20_000 if name == "C3" else 8_000
             res = ia.match_insert_batch(w["reads1"][:k], w["reads2"][:k]).results()
             r1s, r2s = _rows(w["reads1"][:k].cpu()), _rows(w["reads2"][:k].cpu())
@@ -112,8 +117,9 @@ def test_correct_errors_fixture(hip_backend):
 def test_c5_correction_at_size(hip_backend, oracle):
     """BASELINE config C5 at shard-piece size (2 M pairs 2 x 250 bp with qualities, read wildcards):
     insert match + liberal error correction in place (atr_insert_match_batch + atr_insert_correct_batch).
-    The head against the reference's outputs (c5_head.json.gz), a slice of the insert matches against the
-    oracle, and size-independent properties of all 2 M pairs."""
+    The head against the reference's outputs (c5_head.json.gz), all records of the insert matches against the
+    oracle, the corrected bases, qualities, `changed` and `newlen` of all 2 M pairs against insert_correct_many run
+    on the oracle's own records, and size-independent properties of all 2 M pairs."""
     import numpy as np
     import torch
     from atropos_amd import synth
@@ -147,22 +153,26 @@ def test_c5_correction_at_size(hip_backend, oracle):
         for got_s, got_q, exp in ((h1[k], hq1[k], a), (h2[k], hq2[k], b)):
             assert bytes(got_s[:len(exp[0])]).decode() == exp[0] and bytes(got_q[:len(exp[1])]).decode() == exp[1], k
         assert int(ch[k, 0]) == a[2] and int(ch[k, 1]) == b[2]
-    # (2) a slice of the insert matches against the oracle
-    lo, k = 1_234_000, 20_000
+    # (2) all 2 M insert records against the oracle
     orc = oracle.InsertOracle(synth.PE_ADAPTER1, synth.PE_ADAPTER2, read_wildcards=True)
-    lens = np.full(k, 250, np.int32)
-    exp = oracle.match_insert_many(orc, w["reads1"][lo:lo + k].cpu().numpy(), lens, w["reads2"][lo:lo + k].cpu().numpy(), lens, 8)
-    assert np.array_equal(rec[lo:lo + k, :, :6].cpu().numpy().astype(np.int32), exp)
-    # (2b) the corrected bases AND qualities of two slices against the checker's correct_errors (pinned to the
-    #      reference by correct_errors_fuzz.json.gz): 40 k pairs, byte for byte, plus the per-read counts
-    for lo2 in (lo, 0):
-        e1, e2, eq1, eq2 = (np.ascontiguousarray(w[key][lo2:lo2 + k].cpu().numpy()) for key in ("reads1", "reads2", "quals1", "quals2"))
-        exp_rec = exp if lo2 == lo else oracle.match_insert_many(orc, e1, lens, e2, lens, 8)
-        ech, enl = oracle.insert_correct_many(exp_rec, e1, eq1, lens, e2, eq2, lens, "liberal", 1, 8)
-        assert int((ech.sum(axis=1) > 0).sum()) > k // 8
-        for got_t, exp_m in ((s1, e1), (s2, e2), (q1, eq1), (q2, eq2)):
-            assert np.array_equal(got_t[lo2:lo2 + k].cpu().numpy(), exp_m)
-        assert np.array_equal(changed[lo2:lo2 + k].cpu().numpy(), ech) and np.array_equal(newlen[lo2:lo2 + k].cpu().numpy(), enl)
+    exp = _cases.check_insert_all(oracle, orc, rec, w["reads1"], w["reads2"], "C5 correction: insert")
+    # (2b) the corrected bases AND qualities of all 2 M pairs against the checker's correct_errors (pinned to the
+    #      reference by correct_errors_fuzz.json.gz) run on the oracle's own records: byte for byte, plus the
+    #      per-read counts and lengths
+    ncorrected, step = 0, 500_000
+    for lo in range(0, n, step):
+        hi = min(n, lo + step)
+        lens = np.full(hi - lo, 250, np.int32)
+        e1, e2, eq1, eq2 = (np.ascontiguousarray(w[key][lo:hi].cpu().numpy()) for key in ("reads1", "reads2", "quals1", "quals2"))
+        orig1 = e1.copy()                                                # (for the message: read 1 as it was)
+        ech, enl = oracle.insert_correct_many(exp[lo:hi], e1, eq1, lens, e2, eq2, lens, "liberal", 1, _cases.oracle_threads())
+        ncorrected += int((ech.sum(axis=1) > 0).sum())
+        for what, got_t, exp_m in (("bases 1", s1, e1), ("bases 2", s2, e2), ("qualities 1", q1, eq1), ("qualities 2", q2, eq2)):
+            _cases.assert_records_equal(got_t[lo:hi].cpu().numpy(), exp_m, "C5 correction: corrected " + what, orig1, None, lo)
+        _cases.assert_records_equal(changed[lo:hi].cpu().numpy().astype(np.int32), ech, "C5 correction: changed", orig1, None, lo)
+        _cases.assert_records_equal(newlen[lo:hi].cpu().numpy().astype(np.int32), enl, "C5 correction: newlen", orig1, None, lo)
+    assert ncorrected > n // 8
+    del e1, e2, eq1, eq2, orig1, exp
     # (3) properties of all pairs
     assert bool((ch >= 0).all())                                         # no pair failed (KeyError / IndexError / ValueError codes are < 0)
     untouched = ~(found & (errs > 0))

@@ -76,7 +76,7 @@ def test_piece_pipeline_long_adapters(hip_backend, oracle):
         assert torch.equal(rec, al.locate_batch(tiles, path="filtered").records)
         assert torch.equal(rec, al.locate_batch(tiles, filtered=False).records)
         sl = reads[:100_000].cpu().numpy()
-        exp = oracle.locate_many(synth.PE_ADAPTER1, sl, np.full(len(sl), 150, np.int32), e, 14, False, False, 3, 1, 8)
+        exp = oracle.locate_many(synth.PE_ADAPTER1, sl, np.full(len(sl), 150, np.int32), e, 14, False, False, 3, 1, _cases.oracle_threads())
         assert np.array_equal(rec[:100_000, :6].cpu().numpy().astype(np.int32), exp)
         assert 0.4 < float((rec[:, 1] >= 0).float().mean().item()) < 0.7
 
@@ -103,7 +103,7 @@ def test_piece_pipeline_start_within_seq1(hip_backend, oracle):
         tiles = al.pack(reads, layout="tile64")
         assert torch.equal(rec, al.locate_batch(tiles, filtered=False).records)
         sl = reads[:60_000].cpu().numpy()
-        exp = oracle.locate_many(radapter, sl, np.full(len(sl), 150, np.int32), 0.1, flags, False, False, 3, 1, 8)
+        exp = oracle.locate_many(radapter, sl, np.full(len(sl), 150, np.int32), 0.1, flags, False, False, 3, 1, _cases.oracle_threads())
         assert np.array_equal(rec[:60_000, :6].cpu().numpy().astype(np.int32), exp)
         assert 0.3 < float((rec[:, 1] >= 0).float().mean().item()) < 0.8
 
@@ -191,9 +191,9 @@ def test_c1_full_against_oracle(hip_backend, oracle):
 
 
 def test_c2_sample_and_full_size_properties(hip_backend, oracle):
-    """BASELINE config C2 at full size (10 M x 150 bp on the device): a 200 k-read
-    slice bit-exact against the oracle, plus size-independent properties over all
-    10 M records."""
+    """BASELINE config C2 at full size (10 M x 150 bp on the device): all records
+    bit-exact against the oracle (locate_many, in chunks), plus size-independent
+    properties over all 10 M records."""
     from atropos_amd import synth
     from atropos_amd.align import Aligner
     n_total = 10_000_000
@@ -209,17 +209,14 @@ def test_c2_sample_and_full_size_properties(hip_backend, oracle):
     assert torch.equal(rec, al.locate_batch(tiles, path="filtered").records)
     assert torch.equal(rec, al.locate_batch(tiles, filtered=False).records)
     del tiles
-    # (1) slice parity
-    lo = 4_321_000
-    sl = reads[lo:lo + 200_000].cpu().numpy()
-    exp = oracle.locate_many(w["adapter"], sl, np.full(len(sl), 150, np.int32), 0.1, 14, False, False, 3, 1, 8)
-    assert np.array_equal(rec[lo:lo + 200_000, :6].cpu().numpy().astype(np.int32), exp)
+    # (1) parity of all 10 M records
+    nfound = _cases.check_locate_all(oracle, rec, w["adapter"], reads, None, 0.1, 14, False, False, 3, 1, "C2 10 M")
     # (2) invariants of every record
     r = rec.to(torch.int32)
     found = r[:, 1] >= 0
     f = r[found]
     m = len(w["adapter"])
-    assert 0.45 < found.float().mean().item() < 0.60
+    assert 0.45 < found.float().mean().item() < 0.60 and nfound == int(found.sum().item())
     assert bool((f[:, 0] == 0).all())                        # BACK adapter: refstart is always 0
     assert bool(((f[:, 1] > 0) & (f[:, 1] <= m)).all())
     assert bool(((f[:, 2] >= 0) & (f[:, 2] <= f[:, 3]) & (f[:, 3] <= 150)).all())
@@ -230,6 +227,7 @@ def test_c2_sample_and_full_size_properties(hip_backend, oracle):
     # (3) determinism / idempotence: same batch, same records; independent of batch split
     rec2 = al.locate_batch(batch).records
     assert torch.equal(rec, rec2)
+    lo = 4_321_000
     part = al.locate_batch(reads[lo:lo + 100_037]).records
     assert torch.equal(part, rec[lo:lo + 100_037])
     # (4) exact-occurrence property: reads containing the whole adapter verbatim match it with 0 errors
@@ -247,7 +245,7 @@ def test_c2_sample_and_full_size_properties(hip_backend, oracle):
 def test_hard_batches_against_oracle(hip_backend, oracle, kind):
     """The batches C2's friendly generator does not produce (synth.hard_batch; round-5 verdict item 6): 2 M reads where
     every read keeps the exact DP busy -- the two-pass pipeline, the one-pass pipeline and the full sweep agree on every
-    record, a 200 k-read slice is bit-exact against the oracle."""
+    record, and all records are bit-exact against the oracle."""
     from atropos_amd import synth
     from atropos_amd.align import Aligner
     n = 2_000_000
@@ -260,11 +258,9 @@ def test_hard_batches_against_oracle(hip_backend, oracle, kind):
     tiles = al.pack(reads, layout="tile64")
     assert torch.equal(rec, al.locate_batch(tiles, path="filtered").records)
     assert torch.equal(rec, al.locate_batch(tiles, filtered=False).records)
-    lo = 777_000
-    sl = reads[lo:lo + 200_000].cpu().numpy()
-    exp = oracle.locate_many(synth.TRUSEQ_34, sl, np.full(len(sl), 150, np.int32), 0.1, 14, False, False, 3, 1, 8)
-    assert np.array_equal(rec[lo:lo + 200_000, :6].cpu().numpy().astype(np.int32), exp)
+    nfound = _cases.check_locate_all(oracle, rec, synth.TRUSEQ_34, reads, None, 0.1, 14, False, False, 3, 1, "hard " + kind)
     found = float((rec[:, 1] >= 0).float().mean().item())
+    assert nfound == int((rec[:, 1] >= 0).sum().item())
     assert found > (0.4 if kind == "lowcomplex" else 0.99)
     assert left is not None and 0 <= left <= n
 
@@ -287,14 +283,15 @@ def test_pairs_fast_pipeline_vs_oracle(hip_backend, oracle):
 
 
 def test_pairs_fast_at_size(hip_backend, oracle):
-    """2 M C3 pairs and 500 k C5 pairs through atr_locate_pairs_batch (MergeOverlapping's two flag sets): slices
-    against the oracle, and every pair against the full sweep of pairs_core.hpp (atr_locate_pairs_full_batch)."""
+    """2 M C3 pairs and 500 k C5 pairs through atr_locate_pairs_batch (MergeOverlapping's two flag sets): all records
+    against the oracle (locate_pairs_many: the reverse complement of read 2 as the reference of its pair), and every pair
+    against the full sweep of pairs_core.hpp (atr_locate_pairs_full_batch).  (The oracle takes 5.5 s + 4.4 s for the C5
+    pairs of the two flag sets on 16 threads: no pair is left out.)"""
     import numpy as np
     import torch
     from atropos_amd import _lib, synth
     from atropos_amd.align import PairAligner
-    from atropos_amd.util import reverse_complement
-    for config, n, k in (("C3", 2_000_000, 6000), ("C5", 500_000, 3000)):
+    for config, n in (("C3", 2_000_000), ("C5", 500_000)):
         w = synth.workload(config, 11, n, device="cuda")
         for flags in (15, 9):
             pa = PairAligner(0.2, flags, revcomp_ref=True)
@@ -303,14 +300,7 @@ def test_pairs_fast_at_size(hip_backend, oracle):
             qb = pa._pack(w["reads1"], _lib.TABLE_DNA15, be, True)
             # need = 1 everywhere: every alignment matters, and the long reads take the fast pipeline too
             got = pa.locate_batch(rb, qb, need=torch.ones((n,), dtype=torch.int32, device="cuda")).records
-            lo = 123_456
-            r1 = w["reads1"][lo:lo + k].cpu().numpy()
-            r2 = w["reads2"][lo:lo + k].cpu().numpy()
-            sub = got[lo:lo + k, :6].cpu().numpy().astype(np.int32)
-            for i in range(k):
-                exp = oracle.locate(reverse_complement(bytes(r2[i]).decode()), bytes(r1[i]).decode(), 0.2, flags, False, False, 1, 1)
-                g = None if sub[i, 1] < 0 else tuple(int(v) for v in sub[i])
-                assert g == exp, (config, flags, lo + i, g, exp)
+            assert _cases.check_pairs_all(oracle, got, w["reads2"], w["reads1"], 0.2, flags, "pairs %s flags=%d" % (config, flags)) == n
             full = be.locate_pairs_full_batch(rb.packed, rb.lens, rb.max_len, True, qb.packed, qb.lens, qb.max_len, n, 0.2, flags, 1, 1)
             assert torch.equal(got, full), (config, flags)
             # with a bound on the matches: the pairs that reach it keep their record, the others may turn into None
@@ -387,7 +377,7 @@ def test_dpmatrix_debug(hip_backend):
 
 def test_ragged_tail_mode(hip_backend, oracle):
     from atropos_amd.align import Aligner
-    assert _cases.check_ragged_tail_mode(Aligner, oracle, 4, nreads=200_000, oracle_slice=3000) == 1_000_000
+    assert _cases.check_ragged_tail_mode(Aligner, oracle, 4, nreads=200_000) == 1_000_000
 
 
 def test_long_reference(hip_backend):
@@ -440,7 +430,8 @@ def test_per_read_api(hip_backend, oracle):
 
 def test_locate_stream_equals_one_call(hip_backend, oracle):
     """Aligner.locate_stream (consecutive batches on two streams, a workspace each) yields, batch by batch, the records
-    of locate_batch -- plane64 and tile64 batches, equal-length and ragged, in input order."""
+    of locate_batch -- plane64 and tile64 batches, equal-length and ragged, in input order; all records of the whole set
+    against the oracle."""
     import numpy as np
     import torch
     from atropos_amd import synth
@@ -465,9 +456,9 @@ def test_locate_stream_equals_one_call(hip_backend, oracle):
     torch.cuda.synchronize()
     whole = al.locate_batch(reads).records
     assert torch.equal(rec, whole) and torch.equal(gathered, whole.cpu())
-    exp = oracle.locate_many(w["adapter"], reads[:50_000].cpu().numpy(), np.full(50_000, 150, np.int32), w["max_error_rate"], 14,
-                             False, False, w["min_overlap"], w["indel_cost"], 8)
-    assert np.array_equal(rec[:50_000, :6].cpu().numpy().astype(np.int32), exp)
+    nfound = _cases.check_locate_all(oracle, rec, w["adapter"], reads, None, w["max_error_rate"], 14, False, False,
+                                     w["min_overlap"], w["indel_cost"], "locate_stream 1.5 M")
+    assert nfound == int((rec[:, 1] >= 0).sum().item()) and nfound > 0.4 * reads.shape[0]
 
 
 def test_pack_planes_against_numpy(hip_backend):

@@ -234,3 +234,55 @@ def test_qualtrim_fuzz(oracle):
         assert ([s[a:b], q[a:b]] if a < b else ["", ""]) == c["nend"], c
         trimmed += c["qtrim"] != [0, len(q)]
     assert trimmed > 1500
+
+
+def test_locate_pairs_many_equals_locate(oracle):
+    """locate_pairs_many (the threaded driver with a reference per pair, harness only) == locate pair by pair, on random
+    overlapping and unrelated pairs of ragged lengths: every flag set of the callers, wildcards, indel costs, the
+    reverse-complemented reference included, for 1, 3 and 16 threads; a base without complement raises as
+    reverse_complement does."""
+    import random
+    import numpy as np
+    import pytest
+    from tests._cases import mutate, rseq
+    rng = random.Random(2024)
+    total = found = 0
+    for rnd in range(48):
+        npairs = rng.choice([1, 2, 97, 250])
+        flags = rng.choice([15, 9, 14, 11, 0, 3])
+        e, ic, mo = rng.choice([0.1, 0.2]), rng.choice([1, 2, 100000]), rng.choice([1, 3])
+        rc = rnd % 2 == 0
+        wr, wq = (rng.random() < 0.3, rng.random() < 0.3) if not rc else (False, False)
+        alpha = "ACGTN" if (wr or wq or rc) else "ACGT"
+        width = rng.choice([40, 150, 250])
+        refs, queries = [], []
+        for _ in range(npairs):
+            m, n = rng.randint(0, width), rng.randint(0, width)
+            frag = rseq(rng, m + n + 1, alpha)
+            refs.append(frag[:m])
+            queries.append(mutate(rng, frag[rng.randint(0, m):][:n], 0.05)[:n] if rng.random() < 0.8 else rseq(rng, n))
+        stored = [oracle.reverse_complement(r) if rc else r for r in refs]      # what the caller holds: read 2 as sequenced
+        rmat = np.full((npairs, width + 3), ord("#"), np.uint8)                 # bytes past a row's length are never read
+        qmat = np.full((npairs, width), ord("#"), np.uint8)
+        for i, (r, q) in enumerate(zip(stored, queries)):
+            rmat[i, :len(r)] = np.frombuffer(r.encode(), np.uint8)
+            qmat[i, :len(q)] = np.frombuffer(q.encode(), np.uint8)
+        rl = np.array([len(r) for r in refs], np.int32)
+        ql = np.array([len(q) for q in queries], np.int32)
+        exp = np.zeros((npairs, 6), np.int32)
+        exp[:, 1] = -1
+        for i, (r, q) in enumerate(zip(refs, queries)):
+            t = oracle.locate(r, q, e, flags, wr, wq, mo, ic)
+            if t is not None:
+                exp[i] = t
+        for nthreads in (1, 3, 16):
+            got = oracle.locate_pairs_many(rmat, rl, qmat, ql, e, flags, wr, wq, mo, ic, rc, nthreads)
+            assert got.dtype == np.int32 and got.shape == (npairs, 6)
+            bad = np.nonzero((got != exp).any(axis=1))[0]
+            assert len(bad) == 0, (rnd, nthreads, int(bad[0]), refs[bad[0]], queries[bad[0]], got[bad[0]], exp[bad[0]])
+        total += npairs
+        found += int((exp[:, 1] >= 0).sum())
+    assert total > 2000 and found > total // 3
+    with pytest.raises(KeyError):
+        oracle.locate_pairs_many(np.frombuffer(b"ACXT", np.uint8)[None, :], [4], np.frombuffer(b"ACGT", np.uint8)[None, :], [4],
+                                 0.1, 15, revcomp_ref=True)

@@ -37,7 +37,7 @@ for seed in range(first, first + (int(sys.argv[2]) if len(sys.argv) > 2 else 4))
     tot += _cases.check_linked_sets_against_oracle(oracle, seed + 600, 150, reads_per_round=(1, 64, 65, 200, 700))[0]
     tot += _cases.check_plane_guided_correction(n=20_000, seed=seed + 700)
     tot += _cases.check_fused_match_correct(n=8_192, seed=seed + 720)
-    tot += _cases.check_ragged_tail_mode(Aligner, oracle, seed + 800, nreads=40_000, oracle_slice=600)
+    tot += _cases.check_ragged_tail_mode(Aligner, oracle, seed + 800, nreads=40_000)
     tot += _cases.check_piece_pipeline(Aligner, oracle, _lib.AtroposHipError, seed + 900, 120, 300)[0]
     # round 6: adapters of 41 .. 64 bases, START_WITHIN_SEQ1 (flags 11 / 15), the certificates on long and hostile adapters
     tot += _cases.check_piece_pipeline(Aligner, oracle, _lib.AtroposHipError, seed + 910, 60, 300, mrange=(41, 64))[0]
