@@ -187,7 +187,19 @@ PROTOTYPES = {
     "atr_read_stats_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
                              + [C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
     "atr_read_stats_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "atr_detect_create": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.POINTER(C.c_void_p)]),
+    "atr_detect_destroy": (None, [C.c_void_p]),
+    "atr_detect_counter_bytes": (C.c_int64, [C.c_void_p]),
+    "atr_detect_clear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "atr_detect_filter_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "atr_detect_mark_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "atr_detect_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p]),
+    "atr_detect_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+DETECT_MAX_READ = 320                    # atr_detect_*: reads up to here (the complexity table is (len + 1)^2 doubles)
+DETECT_HDR = 8                           # detect_core.hpp: kept, distinct, invalid, overlong, then 4 x nseq counters
 
 FASTQ_ERR_AT, FASTQ_ERR_PLUS, FASTQ_ERR_NAME2, FASTQ_ERR_LENGTH = 1, 2, 3, 4
 DEST_KEEP, DEST_TOO_SHORT, DEST_TOO_LONG, DEST_TOO_MANY_N, DEST_TRIMMED, DEST_UNTRIMMED = range(6)
@@ -951,6 +963,64 @@ class HipBackend(object):
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.atr_read_stats_merge(_ptr(dst), int(dst_max_len), _ptr(src), int(src_max_len),
                                                            int(index_offset), self._stream()), "atr_read_stats_merge")
+
+    # -- known-contaminant detection (atr_detect_*) ---------------------------------------------------------------
+    def detect_create(self, seqs, kmer_size, past_end_bases, thresholds, complexity, max_len):
+        """seqs: list of bytes; thresholds: list of int (-1 = never); complexity: float64 ndarray
+        [max_len + 1, max_len + 1].  Returns the handle."""
+        lens = np.asarray([len(s) for s in seqs], dtype=np.int32)
+        thr = np.asarray(thresholds, dtype=np.int32)
+        cx = np.ascontiguousarray(complexity, dtype=np.float64)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_detect_create(b"".join(seqs), lens.ctypes.data, len(seqs), int(kmer_size),
+                                                        bytes(past_end_bases), len(past_end_bases), thr.ctypes.data,
+                                                        cx.ctypes.data, int(max_len), C.byref(h)), "atr_detect_create")
+        return h
+
+    def detect_destroy(self, h):
+        self.lib.atr_detect_destroy(h)
+
+    def detect_counters(self, h):
+        """A zeroed counter block (int64 tensor; the words are uint64 counters)."""
+        words = _check(self.lib, self.lib.atr_detect_counter_bytes(h), "atr_detect_counter_bytes") // 8
+        block = self.empty((words,), torch.int64)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_detect_clear(h, _ptr(block), self._stream()), "atr_detect_clear")
+        return block
+
+    def detect_filter(self, h, data, records, longest, counters):
+        """(kept int32 [n], hashes int64 [n]) of the records."""
+        n = records.shape[0]
+        kept = self.empty((n,), torch.int32)
+        hashes = self.empty((n,), torch.int64)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_detect_filter_batch(h, _ptr(data), _ptr(records), n, int(longest), _ptr(kept),
+                                                              _ptr(hashes), _ptr(counters), self._stream()),
+                   "atr_detect_filter_batch")
+        return kept, hashes
+
+    def detect_mark(self, h, data, records, kept, order, head, counters):
+        """rep uint8 [m]: 1 for one read of every distinct kept sequence (order / head: int64 [m])."""
+        m = order.shape[0]
+        rep = self.empty((m,), torch.uint8)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_detect_mark_batch(h, _ptr(data), _ptr(records), _ptr(kept), _ptr(order), _ptr(head),
+                                                            m, _ptr(rep), _ptr(counters), self._stream()),
+                   "atr_detect_mark_batch")
+        return rep
+
+    def detect_match(self, h, data, records, kept, order, rep, counters):
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_detect_batch(h, _ptr(data), _ptr(records), _ptr(kept), _ptr(order), _ptr(rep),
+                                                       order.shape[0], _ptr(counters), self._stream()), "atr_detect_batch")
+
+    def detect_read(self, h, counters):
+        """The counter block as a host int64 ndarray."""
+        out = np.zeros((counters.shape[0],), dtype=np.int64)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_detect_read(h, _ptr(counters), out.ctypes.data, self._stream()), "atr_detect_read")
+        return out
 
 
 _backend = None

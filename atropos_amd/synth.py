@@ -289,3 +289,37 @@ def hard_batch(kind, start, count, n=150, adapter=TRUSEQ_34, seed=0xA72050006, d
             raise KeyError(kind)
         out[lo:hi] = base.to(torch.uint8)
     return out
+
+
+def contaminated_fastq(n, seed, contaminants, length=150, through=0.4, duplicates=0.05, with_n=0.01):
+    """FASTQ text of n reads of ``length`` bases as a uint8 numpy matrix [n, record bytes] (``.tobytes()`` is the
+    file): ``through`` of them read through into one of the first three ``contaminants`` at an insert of
+    20 .. length - 5, ``duplicates`` are exact copies of an earlier read, ``with_n`` hold one N.  The workload of the
+    detect tests and of tools/bench_detect.py; the sequence of read r is row[3:3 + length]."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    seqs = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=(n, length))
+    adapters = [np.frombuffer(s.encode(), dtype=np.uint8) for s in contaminants[:3]]
+    which = rng.integers(0, len(adapters), n)
+    insert = rng.integers(20, length - 5, n)
+    is_through = rng.random(n) < through
+    col = np.arange(length)[None, :]
+    for a, ad in enumerate(adapters):
+        for lo in range(0, n, 1 << 20):                           # (in pieces: the index matrices are 8 bytes a base)
+            rows = lo + np.nonzero((is_through & (which == a))[lo:lo + (1 << 20)])[0]
+            rel = col - insert[rows, None]
+            inside = (rel >= 0) & (rel < len(ad))
+            sub = seqs[rows]
+            sub[inside] = ad[np.clip(rel, 0, len(ad) - 1)][inside]
+            seqs[rows] = sub
+    holds_n = np.nonzero(rng.random(n) < with_n)[0]
+    seqs[holds_n, rng.integers(0, length, len(holds_n))] = ord("N")
+    dup = np.nonzero(rng.random(n) < duplicates)[0]
+    dup = dup[dup > 0]
+    seqs[dup] = seqs[rng.integers(0, dup)]
+    rec = np.full((n, 3 + length + 3 + length + 1), ord("I"), dtype=np.uint8)
+    rec[:, 0:3] = np.frombuffer(b"@r\n", dtype=np.uint8)
+    rec[:, 3:3 + length] = seqs
+    rec[:, 3 + length:6 + length] = np.frombuffer(b"\n+\n", dtype=np.uint8)
+    rec[:, -1] = ord("\n")
+    return rec

@@ -729,6 +729,53 @@ int atr_read_stats_batch(void *d_stats, int max_len, int longest, int quality_ba
 int atr_read_stats_merge(void *d_dst, int dst_max_len, const void *d_src, int src_max_len, int64_t index_offset,
                          void *stream);
 
+
+/* Known-contaminant detection (KnownContaminantDetector, commands/detect/__init__.py:495-549; atropos detect
+ * --detector known) over a device-resident FASTQ chunk.
+ *
+ * atr_detect_create builds the detector from nseq known sequences (their bytes back to back in `seqs`, lengths in
+ * `lens`): the table of their distinct k-mers and the reverse complements of those.  past_end_bases: n_past_end
+ * single bytes B, a read is cut at the leftmost match of `B{8,}.*|B{2,}$`.  thresholds[s]: the smallest n that counts
+ * as a hit of sequence s (n / n_kmers > min_kmer_match_frac, evaluated by the caller in the reference's floats;
+ * -1 = never).  complexity: doubles [(max_len + 1)][(max_len + 1)], complexity[len][count] = (count / len) *
+ * log(count / len) / log(2) as the reference computes it; the device adds the four entries of a read in IEEE double.
+ * ATR_ERR_UNSUPPORTED: kmer_size outside 4 .. 32 or too long for a 64-bit key with the alphabet of the known
+ * sequences (16 bases at up to 16 letters), more than 128 distinct k-mers in one known sequence, more known sequences
+ * than the match kernel's 64 KiB of LDS hold (818 when none has more than 32 distinct k-mers, 556 up to 64, 421 up to
+ * 96, 339 up to 128), more than 4 past-end bases, max_len > 320.  Argument errors are
+ * reported before the device is touched.
+ *
+ * The results live in a caller-allocated block of atr_detect_counter_bytes() bytes of uint64 counters (zeroed by
+ * atr_detect_clear) that stays on the device across calls: [0] reads kept by the filter, [1] distinct kept
+ * sequences, [2] representatives with a byte that has no complement (the reference raises KeyError), [3] reads
+ * longer than max_len; from word 8 on, nseq words each of: matches (sum of n over the distinct sequences), hits
+ * (distinct sequences with n >= threshold), max_n (largest n among the hits), abundance (distinct sequences that
+ * hold the whole known sequence).  All are sums and maxima of integers: independent of launch shape and order.
+ *
+ * One chunk takes three calls, with a sort by the caller in between:
+ *   atr_detect_filter_batch  d_kept[r] = length the read keeps (0 = dropped), d_hashes[r] = hash of the kept bytes.
+ *                            longest: upper bound of the read lengths; ATR_ERR_UNSUPPORTED beyond max_len, before
+ *                            anything is launched or counted.
+ *   atr_detect_mark_batch    d_order[m]: the kept reads sorted by hash, d_head[i]: index in d_order of the first
+ *                            read with the hash of entry i.  d_rep[i] = 1 for one read of every distinct kept
+ *                            sequence; reads that share a hash are compared byte for byte.
+ *   atr_detect_batch         matches the representatives against the known sequences and adds to the counters.
+ * Distinctness is per call: a caller that wants it over several chunks puts them into one batch.
+ * atr_detect_read copies the block to host memory and waits for the stream. */
+int atr_detect_create(const uint8_t *seqs, const int32_t *lens, int nseq, int kmer_size, const uint8_t *past_end_bases,
+                      int n_past_end, const int32_t *thresholds, const double *complexity, int max_len, void **out);
+void atr_detect_destroy(void *detect);
+int64_t atr_detect_counter_bytes(const void *detect);
+int atr_detect_clear(const void *detect, void *d_counters, void *stream);
+int atr_detect_filter_batch(const void *detect, const uint8_t *d_bytes, const atr_fastq_record *d_records, int64_t n,
+                            int longest, int32_t *d_kept, int64_t *d_hashes, void *d_counters, void *stream);
+int atr_detect_mark_batch(const void *detect, const uint8_t *d_bytes, const atr_fastq_record *d_records,
+                          const int32_t *d_kept, const int64_t *d_order, const int64_t *d_head, int64_t m, uint8_t *d_rep,
+                          void *d_counters, void *stream);
+int atr_detect_batch(const void *detect, const uint8_t *d_bytes, const atr_fastq_record *d_records, const int32_t *d_kept,
+                     const int64_t *d_order, const uint8_t *d_rep, int64_t m, void *d_counters, void *stream);
+int atr_detect_read(const void *detect, const void *d_counters, uint64_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
