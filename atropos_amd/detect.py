@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .fastq import FastqBatch, read_chunks
 
 LOG2 = math.log(2)
 MAX_READ = _lib.DETECT_MAX_READ
@@ -202,7 +203,6 @@ def _check_past_end(past_end_bases):
 
 def _concat(batches):
     """The batches as one: their texts back to back, the records' offsets shifted."""
-    from .fastq import FastqBatch
     if len(batches) == 1:
         return batches[0]
     be = batches[0].backend
@@ -445,6 +445,10 @@ class PairedDetector(object):
         self.read1_detector.add_batch(batch1)
         self.read2_detector.add_batch(batch2)
 
+    def close(self):
+        self.read1_detector.close()
+        self.read2_detector.close()
+
     def matches(self, **kwargs):
         return self.read1_detector.matches(**kwargs), self.read2_detector.matches(**kwargs)
 
@@ -455,52 +459,35 @@ class PairedDetector(object):
 
 
 # ---------------------------------------------------------------------------------------------- file drivers
-def _feed(paths, detector, max_reads, chunk_bytes):
-    from .stats import _stream
-    left = [max_reads]
-
-    class _Done(Exception):
-        pass
-
-    def each(*batches):
-        if left[0] is not None:
-            batches = [b.head(left[0])[0] for b in batches]
-            left[0] -= len(batches[0])
-        detector.add_batch(*batches)
-        if left[0] is not None and left[0] <= 0:
-            raise _Done()
-
+def _detect_paths(paths, detector_class, known_contaminants, max_reads, chunk_bytes, kwargs):
+    """The chunks of ``fastq.read_chunks`` into a detector until ``max_reads`` records went in; its summary."""
+    report = {k: kwargs.pop(k) for k in ("min_len", "min_complexity", "min_match_frac", "limit") if k in kwargs}
+    kwargs.setdefault("n_reads", max_reads)
+    det = detector_class(known_contaminants, **kwargs)
     try:
-        _stream(paths, chunk_bytes, each)
-    except _Done:
-        pass
+        left = max_reads
+        for batches in read_chunks(paths, chunk_bytes):
+            if left is not None:
+                batches = [b.head(left)[0] for b in batches]
+                left -= len(batches[0])
+            det.add_batch(*batches)
+            if left is not None and left <= 0:
+                break
+        return det.summarize(**report)
+    finally:
+        det.close()
 
 
 def detect_file(path, known_contaminants, max_reads=10000, chunk_bytes=64 << 20, **kwargs):
     """``atropos detect --detector known`` of one FASTQ file, read in chunks, stopping after ``max_reads`` records
     (None: the whole file, which must fit one batch -- see the module doc).  ``n_reads`` defaults to ``max_reads``.
     Returns the reference's ``summary['detect']`` dict; ``matches`` is a 1-tuple of lists."""
-    report = {k: kwargs.pop(k) for k in ("min_len", "min_complexity", "min_match_frac", "limit") if k in kwargs}
-    kwargs.setdefault("n_reads", max_reads)
-    det = KnownContaminantDetector(known_contaminants, **kwargs)
-    try:
-        _feed([path], det, max_reads, chunk_bytes)
-        return det.summarize(**report)
-    finally:
-        det.close()
+    return _detect_paths([path], KnownContaminantDetector, known_contaminants, max_reads, chunk_bytes, kwargs)
 
 
 def detect_files(path1, path2, known_contaminants, max_reads=10000, chunk_bytes=64 << 20, **kwargs):
     """The same for paired files: ``matches`` is a 2-tuple of lists, one per read."""
-    report = {k: kwargs.pop(k) for k in ("min_len", "min_complexity", "min_match_frac", "limit") if k in kwargs}
-    kwargs.setdefault("n_reads", max_reads)
-    det = PairedDetector(known_contaminants, **kwargs)
-    try:
-        _feed([path1, path2], det, max_reads, chunk_bytes)
-        return det.summarize(**report)
-    finally:
-        det.read1_detector.close()
-        det.read2_detector.close()
+    return _detect_paths([path1, path2], PairedDetector, known_contaminants, max_reads, chunk_bytes, kwargs)
 
 
 def detect_from_args(argv, paired=False):

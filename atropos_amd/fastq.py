@@ -7,7 +7,10 @@ A chunk of the file is uploaded as raw bytes; the library finds and validates th
 surviving records are formatted on the device (``atr_fastq_emit``).  No per-read Python
 object exists anywhere on this path.
 """
+import collections
 import os
+import time
+from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
@@ -324,7 +327,6 @@ class StageClock(object):
         self.seconds = {}
 
     def add(self, stage, t0):
-        import time
         self.seconds[stage] = self.seconds.get(stage, 0.0) + (time.perf_counter() - t0)
 
 
@@ -344,15 +346,19 @@ class ChunkedFastqReader(object):
     Python run against the caller's -- and is not kept.)
 
     ``.gz`` / ``.bz2`` / ``.xz`` input (what the reference's xopen opens by extension) is decompressed by one
-    read-ahead thread straight into the staging buffer: the decompressor then sets the pace."""
+    read-ahead thread straight into the staging buffer: the decompressor then sets the pace.
+
+    ``byte_range`` = (lo, hi): only these bytes of a plain file, which must be whole records (a rank's shard,
+    ``shard.fastq_shard_ranges``).  The loop that drives a reader -- ``next_batch``, ``advance``, ``close``, and two
+    readers in lock step -- is ``read_chunks``; nothing else constructs one."""
 
     READ_AHEAD = 3
     RESERVE = 64 << 20                                       # room for the carried-over tail of the previous chunk
 
-    def __init__(self, path, chunk_bytes, backend=None, clock=None):
-        import collections
-        import os
-        from concurrent.futures import ThreadPoolExecutor
+    def __init__(self, path, chunk_bytes, backend=None, clock=None, byte_range=None):
+        name = str(path)
+        if byte_range is not None and name.endswith((".gz", ".bz2", ".xz")):
+            raise ValueError("a byte range of compressed input: the offsets are those of the plain text")
         self.be = backend or _lib.get_backend()
         self.clock = clock or StageClock()
         self.chunk_bytes = int(chunk_bytes)
@@ -360,10 +366,8 @@ class ChunkedFastqReader(object):
         pinned = getattr(self.be, "name", "") == "hip"
         self.file = open(path, "rb")
         self.fd = self.file.fileno()
-        self.size = os.path.getsize(path)
-        self.pos = 0
+        self.pos, self.size = byte_range or (0, os.path.getsize(path))      # (plain files: the next pread, the end)
         self.stream = None
-        name = str(path)
         if name.endswith(".gz"):
             import gzip
             self.stream = gzip.open(self.file, "rb")
@@ -396,7 +400,6 @@ class ChunkedFastqReader(object):
 
     # ---- plain files: reads ahead of the carry
     def _issue_read(self):
-        import os
         if self.read_done:
             return
         slot = self.next_slot
@@ -423,7 +426,6 @@ class ChunkedFastqReader(object):
 
     def _assemble(self, carry):
         """The next chunk: its carried-over head in front of the bytes read for it, and its upload."""
-        import time
         t0 = time.perf_counter()
         if self.reads:
             slot, jobs, want, final = self.reads.popleft()
@@ -497,7 +499,6 @@ class ChunkedFastqReader(object):
 
     def next_batch(self):
         """Upload and index the next chunk; returns the FastqBatch of its whole records."""
-        import time
         t0 = time.perf_counter()
         res = self.pending.result() if hasattr(self.pending, "result") else self.pending
         self.nbytes, self.final, unterminated, data, ready, self.host = res
@@ -549,6 +550,42 @@ class ChunkedFastqReader(object):
         self.buf = []
 
 
+def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None):
+    """THE chunk loop of every file driver (trim, qc, error rate, detect, a rank's shard): yields a list of
+    FastqBatch, one per path, chunk after chunk of whole records.  Several paths are read in lock step: every
+    batch of a list holds the same number of records (the file whose chunk holds fewer decides, the surplus of the
+    others is carried over), and files that do not hold the same number of records are a ValueError.
+
+    The next chunk is put together, and its upload started, BEFORE a chunk is handed out: that copy runs while the
+    consumer works.  A chunk may hold no whole record; it is yielded all the same.  The readers are closed when the
+    loop ends, however it ends -- a consumer that has enough just leaves its ``for`` loop.  ``byte_ranges``: one
+    (lo, hi) or None per path (``ChunkedFastqReader``)."""
+    mismatch = "the two input files hold different numbers of records"
+    readers = []
+    try:
+        for path, byte_range in zip(paths, byte_ranges or [None] * len(paths)):
+            readers.append(ChunkedFastqReader(path, chunk_bytes, backend, clock, byte_range))
+        while True:
+            batches = [r.next_batch() for r in readers]
+            if len(readers) == 1:
+                done = [readers[0].advance()]                 # (all whole records: no head(), no device sync)
+            else:
+                nrec = min(len(b) for b in batches)
+                heads = [b.head(nrec) for b in batches]
+                done = [r.advance(h[1]) for r, h in zip(readers, heads)]
+                if all(r.final for r in readers) and any(len(b) != nrec for b in batches):
+                    raise ValueError(mismatch)
+                batches = [h[0] for h in heads]
+            yield batches
+            if all(done):
+                return
+            if any(done):
+                raise ValueError(mismatch)
+    finally:
+        for r in readers:
+            r.close()
+
+
 class FastqSink(object):
     """Writes device text to a file through three page-locked buffers.  ``write`` only queues: the
     device -> host copy runs on its own stream behind an event (the caller's stream goes on with the
@@ -576,8 +613,6 @@ class FastqSink(object):
         cls.WRITERS = max(1, int(n))
 
     def __init__(self, path, capacity, backend=None, clock=None, keep=False, direct=False, nbuf=3):
-        import os
-        from concurrent.futures import ThreadPoolExecutor
         be = backend or _lib.get_backend()
         self.clock = clock or StageClock()
         self.gpu = getattr(be, "name", "") == "hip"
@@ -605,7 +640,6 @@ class FastqSink(object):
         self.copy_stream = torch.cuda.Stream(device=be.device) if self.gpu else None
 
     def _put(self, k, rem, n, offset, done, text):
-        import os
         if done is not None:
             done.synchronize()                                # the device -> host copy has landed
         del text
@@ -640,7 +674,6 @@ class FastqSink(object):
             self.buf[(k + 1) % self.nbuf][:total - whole].copy_(host[whole:total])
 
     def write(self, text):
-        import time
         n = int(text.numel())
         room = self.buf[self.k].numel() - self.BLOCK           # (a staging buffer also holds up to BLOCK - 1 carried bytes)
         if n > room:
@@ -675,8 +708,6 @@ class FastqSink(object):
         self.k = (self.k + 1) % self.nbuf
 
     def close(self):
-        import os
-        import time
         t0 = time.perf_counter()
         try:
             for job in self.pending:
@@ -744,7 +775,6 @@ class CompressedSink(object):
     One host thread compresses -- it sets the pace of the whole run (pigz-style parallel blocks: the caller's pipe)."""
 
     def __init__(self, path, clock=None):
-        from concurrent.futures import ThreadPoolExecutor
         name = str(path)
         if name.endswith(".gz"):
             import gzip
@@ -760,7 +790,6 @@ class CompressedSink(object):
         self.pending = []
 
     def write(self, text):
-        import time
         t0 = time.perf_counter()
         while len(self.pending) > 2:                          # (bounded: at most three chunks in flight)
             self.pending.pop(0).result()

@@ -8,6 +8,11 @@ them in one place they are copied to host memory and gathered over a host-side (
 group in shard order, which keeps output order == input order (the reference's
 ``--preserve-order``).
 """
+import contextlib
+import os
+import threading
+import time
+
 import torch
 
 
@@ -98,9 +103,6 @@ def sharded_run_threads(backends, total, work, out_shape, out_dtype=torch.int16)
     into ONE host buffer (page-locked when a GPU is present) at its shard's offset.
     ``work(lo, hi)`` runs in the device's thread, inside ``_lib.thread_backend(backends[d])``, and
     returns that shard's record tensor.  Returns (host tensor [total, *out_shape], seconds per device)."""
-    import contextlib
-    import threading
-    import time
     from . import _lib
     world = len(backends)
     out = torch.empty((total,) + tuple(out_shape), dtype=out_dtype)
@@ -165,7 +167,6 @@ def fastq_record_start(path, offset, probe=1 << 20):
     that starts with '@', whose line after next starts with '+' and whose sequence and quality
     lines have the same length -- a quality line may itself start with '@', the record shape
     does not."""
-    import os
     size = os.path.getsize(path)
     if offset <= 0:
         return 0
@@ -190,7 +191,6 @@ def fastq_record_start(path, offset, probe=1 << 20):
 
 def fastq_shard_ranges(path, world):
     """[lo, hi) byte ranges of ``world`` contiguous shards of whole records."""
-    import os
     size = os.path.getsize(path)
     cuts = [fastq_record_start(path, size * r // world) for r in range(world)] + [size]
     # A probe that finds no record boundary (very long or multi-line records) answers `size`: such a
@@ -203,29 +203,13 @@ def fastq_shard_ranges(path, world):
 
 def sharded_trim_file(pipeline, path_in, path_out, rank=None, world=None, chunk_bytes=256 << 20):
     """Every rank runs ``pipeline`` (atropos_amd.trim.TrimPipeline) over its own shard of
-    ``path_in`` and writes ``path_out + ".part%d" % rank``; the parts concatenated in rank order are
+    ``path_in`` (a plain file: the shards are byte ranges) and writes ``path_out + ".part%d" % rank``, as
+    ``trim_file`` would a file that held the shard alone; the parts concatenated in rank order are
     the output of a single-process run.  Returns this rank's destination counts."""
     import torch.distributed as dist
-    from . import _lib
-    from .fastq import FastqBatch
+    from .trim import _trim_stream
     if rank is None:
         rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
-    lo, hi = fastq_shard_ranges(path_in, world)[rank]
-    totals = None
-    with open(path_in, "rb") as fin, open("%s.part%d" % (path_out, rank), "wb") as fout:
-        fin.seek(lo)
-        left, carry = hi - lo, b""
-        while True:
-            block = fin.read(min(chunk_bytes, left))
-            left -= len(block)
-            final = left == 0
-            batch, consumed = FastqBatch.from_bytes(carry + block, final=final)
-            carry = b"" if final else (carry + block)[consumed:]
-            res = pipeline.run(batch)
-            fout.write(res.text(_lib.DEST_KEEP))
-            counts = res.counts()
-            totals = counts if totals is None else {k: totals[k] + v for k, v in counts.items()}
-            if final:
-                break
-    return totals
-
+    byte_range = fastq_shard_ranges(path_in, world)[rank]
+    return _trim_stream(pipeline, [path_in], ["%s.part%d" % (path_out, rank)], chunk_bytes, keep_output=False,
+                        output_parts=1, byte_ranges=[byte_range])

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fastq import FastqBatch
+from .fastq import FastqBatch, read_chunks
 
 HDR = 8                                     # stats_core.hpp
 COUNT, LONGEST, WITHQ, SKIPPED = range(4)
@@ -303,40 +303,20 @@ class PairedEndReadStatistics(object):
 
 
 # ---------------------------------------------------------------------------------------------- file drivers
-def _stream(paths, chunk_bytes, each):
-    """Chunks of whole records of one file, or of two files in lock step (the same number of records from each)."""
-    from .fastq import ChunkedFastqReader
-    be = _lib.get_backend()
-    readers = [ChunkedFastqReader(p, chunk_bytes, be) for p in paths]
-    try:
-        while True:
-            batches = [r.next_batch() for r in readers]
-            nrec = min(len(b) for b in batches)
-            heads = [b.head(nrec) for b in batches]
-            done = [r.advance(h[1]) for r, h in zip(readers, heads)]
-            if all(r.final for r in readers) and len(set(len(b) for b in batches)) > 1:
-                raise ValueError("the two input files hold different numbers of records")
-            each(*[h[0] for h in heads])
-            if all(done):
-                return
-            if any(done):
-                raise ValueError("the two input files hold different numbers of records")
-    finally:
-        for r in readers:
-            r.close()
-
-
+# (every chunk of ``fastq.read_chunks`` into the counters: one file, or two in lock step)
 def qc_file(path, chunk_bytes=64 << 20, quality_base=33, qualities=True):
     """``atropos qc`` of one FASTQ file: {"pre": {0: {"read1": summary}}} (QcPipeline.finish)."""
     st = SingleEndReadStatistics(qualities=qualities, quality_base=quality_base)
-    _stream([path], chunk_bytes, lambda b: st.collect_batch(b))
+    for batches in read_chunks([path], chunk_bytes):
+        st.collect_batch(*batches)
     return {"pre": {0: st.summarize()}}
 
 
 def qc_files(path1, path2, chunk_bytes=64 << 20, quality_base=33, qualities=True):
     """``atropos qc`` of paired files: {"pre": {0: {"read1": ..., "read2": ...}}}."""
     st = PairedEndReadStatistics(qualities=qualities, quality_base=quality_base)
-    _stream([path1, path2], chunk_bytes, lambda b1, b2: st.collect_batch(b1, b2))
+    for batches in read_chunks([path1, path2], chunk_bytes):
+        st.collect_batch(*batches)
     return {"pre": {0: st.summarize()}}
 
 
@@ -345,6 +325,8 @@ def error_rate_file(path, path2=None, max_bases=None, chunk_bytes=64 << 20):
     BaseQualityErrorEstimator / PairedErrorEstimator put them in the summary."""
     paths = [path] if path2 is None else [path, path2]
     sts = [ReadStatistics(qualities=True) for _ in paths]
-    _stream(paths, chunk_bytes, lambda *bs: [s.collect_batch(b) for s, b in zip(sts, bs)])
+    for batches in read_chunks(paths, chunk_bytes):
+        for st, batch in zip(sts, batches):
+            st.collect_batch(batch)
     res = [s.error_rate(max_bases) for s in sts]
     return tuple(r[0] for r in res), tuple(r[1] for r in res)

@@ -27,11 +27,13 @@ too-short / too-long / untrimmed outputs, and make the --stats pre / post summar
 cover (options ``pipeline_from_args`` does not know, and the combinations the constructors refuse) raises instead
 of silently differing; those stay on the per-read object path (``atropos_amd.modifiers``).
 """
+import time
+
 import torch
 
 from . import _lib
 from .adapters import LinkedAdapter
-from .fastq import FastqBatch, RecordSource, open_by_extension
+from .fastq import FastqBatch, RecordSource, StageClock, make_sink, open_by_extension, read_chunks
 
 DEST_MERGED = 6              # MergedReadFilter (filters.py:109-113): installed first, so a merged pair goes nowhere else
 DEST_NAMES = {_lib.DEST_KEEP: "keep", _lib.DEST_TOO_SHORT: "too_short", _lib.DEST_TOO_LONG: "too_long",
@@ -266,11 +268,10 @@ def _run_stages(pipes, mates, insert_stage=None):
     return found
 
 
-def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out=None):
-    """The file loop of ``TrimPipeline.trim_file`` (one input) and ``PairedTrimPipeline.trim_files`` (two inputs in
-    lock step: the same number of records from each file per chunk); returns the destination counts."""
-    import time
-    from .fastq import ChunkedFastqReader, StageClock, make_sink
+def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out=None, byte_ranges=None):
+    """What ``TrimPipeline.trim_file`` (one input), ``PairedTrimPipeline.trim_files`` (two inputs in lock step) and
+    ``shard.sharded_trim_file`` (``byte_ranges``: a rank's part of the input) do with every chunk of
+    ``fastq.read_chunks``; returns the destination counts."""
     paired = len(paths_in) == 2
     first = pipe.p1 if paired else pipe
     merging = paired and pipe.merge_overlapping
@@ -278,7 +279,6 @@ def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
     be = _lib.get_backend()
     totals = {name: 0 for name in DEST_NAMES.values()}
     clock = StageClock()
-    readers = [ChunkedFastqReader(p, chunk_bytes, be, clock) for p in paths_in]
     sinks = [make_sink(p, output_parts, chunk_bytes + (64 << 20) + 32, be, clock, keep=keep_output) for p in paths_out]
     aux_files = {kind: open_by_extension(path) for kind, path in (pipe.aux or {}).items()}
     dest_codes = {name: code for code, name in DEST_NAMES.items()}
@@ -291,17 +291,7 @@ def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
             sinks.append(make_sink(merged_out, output_parts, 2 * (chunk_bytes + (64 << 20)) + 32, be, clock, keep=keep_output))
     stats = TrimStats(pipe.stats, paired, first.quality_base) if pipe.stats else None
     try:
-        while True:
-            batches = [r.next_batch() for r in readers]
-            if paired:
-                nrec = min(len(batches[0]), len(batches[1]))
-                heads = [batches[k].head(nrec) for k in range(2)]
-                done = [readers[k].advance(heads[k][1]) for k in range(2)]
-                if all(r.final for r in readers) and len(batches[0]) != len(batches[1]):
-                    raise ValueError("the two input files hold different numbers of records")
-                batches = [h[0] for h in heads]
-            else:
-                done = [readers[0].advance()]                 # starts reading the next chunk
+        for batches in read_chunks(paths_in, chunk_bytes, be, clock, byte_ranges):
             t0 = time.perf_counter()
             if stats is not None and stats.pre is not None:
                 stats.pre.collect_batch(*batches)             # before any stage writes into the chunks
@@ -327,14 +317,10 @@ def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
                     fh.write(r.text(code))
             for name, v in counts.items():
                 totals[name] += v
-            if all(done):
-                break
-            if any(done):
-                raise ValueError("the two input files hold different numbers of records")
         if stats is not None:
             pipe.stats_summary = stats.summary()
     finally:
-        for obj in readers + sinks + list(aux_files.values()) + [fh for fhs in dest_files.values() for fh in fhs]:
+        for obj in sinks + list(aux_files.values()) + [fh for fhs in dest_files.values() for fh in fhs]:
             obj.close()
         pipe.stage_seconds = dict(clock.seconds)
     return totals
@@ -660,7 +646,7 @@ class TrimPipeline(object):
     def trim_file(self, path_in, path_out, chunk_bytes=256 << 20, keep_output=False, output_parts=1):
         """Stream a FASTQ file through the GPU in chunks of whole records; returns the
         destination counts.  (Plain files; compressed input is the caller's business.)
-        Host side: ``ChunkedFastqReader`` / ``FastqSink`` (page-locked staging buffers, threaded
+        Host side: ``fastq.read_chunks`` (the one chunk loop, over ``ChunkedFastqReader``) / ``FastqSink`` (page-locked staging buffers, threaded
         reads, read-ahead; device -> host copies on their own stream and write-behind, so the GPU
         works on chunk i + 1 while chunk i travels back and into the file).  ``keep_output``: overwrite
         an existing output file in place instead of truncating it first.  ``output_parts`` > 1: the output

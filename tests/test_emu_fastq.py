@@ -113,3 +113,147 @@ def test_chunked_reader_read_ahead_and_carry(emu_backend, tmp_path):
             reader.close()
         assert chunks > 2 * (ChunkedFastqReader.READ_AHEAD + 1)
         assert b"".join(got) == (text + "\n").encode()
+
+
+def _fastq_text(n, min_len, max_len, seed, eol="\n", tag=""):
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    recs = []
+    for i in range(n):
+        m = int(rng.integers(min_len, max_len + 1))
+        seq = "".join("ACGT"[k] for k in rng.integers(0, 4, m))
+        recs.append("@read%d%s\n%s\n+\n%s\n" % (i, tag, seq, "I" * m))
+    return "".join(recs).replace("\n", eol).encode()
+
+
+def _chunk_records(batch):
+    return [(name, seq, qual) for name, seq, qual, _ in batch.to_records()]
+
+
+def _text_records(text):
+    lines = text.replace(b"\r\n", b"\n").decode().split("\n")
+    return [(lines[i][1:], lines[i + 1], lines[i + 3]) for i in range(0, len(lines) - 3, 4)]
+
+
+def test_read_chunks_one_file(emu_backend, tmp_path):
+    """fastq.read_chunks over one file in many small chunks: every record once and in order, with "\\n" and
+    "\\r\\n" line ends and with a last record that has no line end."""
+    from atropos_amd.fastq import read_chunks
+    for k, (eol, cut) in enumerate((("\n", 0), ("\r\n", 0), ("\n", 1), ("\r\n", 2))):
+        text = _fastq_text(500, 20, 90, 3 + k, eol)
+        text = text[:len(text) - cut]                          # (cut: the last line end is missing)
+        path = tmp_path / ("in%d.fastq" % k)
+        path.write_bytes(text)
+        got, chunks = [], 0
+        for batches in read_chunks([str(path)], 4096, emu_backend):
+            assert len(batches) == 1
+            got += _chunk_records(batches[0])
+            chunks += 1
+        assert chunks > 8
+        assert got == _text_records(text)
+        assert len(got) == 500
+
+
+def test_read_chunks_two_files_in_lock_step(emu_backend, tmp_path):
+    """Short R1 records next to R2 records of more than twice their size: every pair of batches holds the same
+    number of records and nothing is lost."""
+    from atropos_amd.fastq import read_chunks
+    text1, text2 = _fastq_text(600, 20, 40, 5, tag="/1"), _fastq_text(600, 150, 250, 6, tag="/2")
+    assert len(text2) > 2 * len(text1)
+    paths = [str(tmp_path / "r1.fastq"), str(tmp_path / "r2.fastq")]
+    for p, t in zip(paths, (text1, text2)):
+        open(p, "wb").write(t)
+    got1, got2, chunks = [], [], 0
+    for b1, b2 in read_chunks(paths, 8192, emu_backend):
+        assert len(b1) == len(b2)
+        got1 += _chunk_records(b1)
+        got2 += _chunk_records(b2)
+        chunks += 1
+    assert chunks > 8
+    assert got1 == _text_records(text1) and got2 == _text_records(text2)
+    assert len(got1) == len(got2) == 600
+
+
+def test_read_chunks_unequal_record_counts(emu_backend, tmp_path):
+    """Two files with different numbers of records are a ValueError: when the shorter file ends many chunks before
+    the other, and when both end in the same chunk."""
+    import pytest
+    from atropos_amd.fastq import read_chunks
+    full = _fastq_text(400, 50, 60, 7)
+    ends = [i + 1 for i, c in enumerate(full) if c == 10][3::4]             # the byte behind every record
+    paths = [str(tmp_path / "r1.fastq"), str(tmp_path / "r2.fastq")]
+    open(paths[0], "wb").write(full)
+    for nrec, chunk_bytes, chunks_before in ((150, 4096, 4), (399, 4096, 4), (399, 1 << 20, 0)):
+        open(paths[1], "wb").write(full[:ends[nrec - 1]])
+        seen = 0
+        with pytest.raises(ValueError, match="^the two input files hold different numbers of records$"):
+            for b1, b2 in read_chunks(paths, chunk_bytes, emu_backend):
+                assert len(b1) == len(b2)
+                seen += 1
+        assert seen >= chunks_before
+    for order in (paths, paths[::-1]):                         # (both files whole in one chunk, either one short)
+        with pytest.raises(ValueError, match="different numbers of records"):
+            for _ in read_chunks(order, 1 << 20, emu_backend):
+                raise AssertionError("a chunk of files that do not match was handed out")
+
+
+def test_read_chunks_closes_the_readers_when_the_consumer_leaves(emu_backend, tmp_path, monkeypatch):
+    """A consumer that breaks out of the loop (or raises in it) leaves no reader open: staging buffers handed back,
+    file closed."""
+    import pytest
+    from atropos_amd import fastq
+    made = []
+
+    class Recorded(fastq.ChunkedFastqReader):
+        def __init__(self, *args, **kwargs):
+            super().__init__(*args, **kwargs)
+            made.append(self)
+
+    monkeypatch.setattr(fastq, "ChunkedFastqReader", Recorded)
+    paths = [str(tmp_path / "r1.fastq"), str(tmp_path / "r2.fastq")]
+    for k, p in enumerate(paths):
+        open(p, "wb").write(_fastq_text(500, 30, 80, 8 + k))
+    for batches in fastq.read_chunks(paths, 4096, emu_backend):
+        assert len(made) == 2 and all(r.buf and not r.file.closed for r in made)
+        break
+    assert len(made) == 2 and all(r.buf == [] and r.file.closed for r in made)
+    del made[:]
+    with pytest.raises(KeyError):
+        for batches in fastq.read_chunks(paths[:1], 4096, emu_backend):
+            raise KeyError("the consumer fails")
+    assert len(made) == 1 and made[0].buf == [] and made[0].file.closed
+
+
+def test_read_chunks_byte_ranges(emu_backend, tmp_path):
+    """A byte range of shard.fastq_shard_ranges yields the records of that range and no other, for every shard of a
+    3-way split and for an empty shard; compressed input has no byte ranges."""
+    import gzip
+    import pytest
+    from atropos_amd.fastq import read_chunks
+    from atropos_amd.shard import fastq_shard_ranges
+    text = _fastq_text(700, 20, 90, 10)
+    path = str(tmp_path / "in.fastq")
+    open(path, "wb").write(text)
+    ranges = fastq_shard_ranges(path, 3)
+    assert all(hi > lo for lo, hi in ranges)
+    whole = []
+    for lo, hi in ranges + [(ranges[1][0], ranges[1][0]), (len(text), len(text))]:
+        got, chunks = [], 0
+        for (batch,) in read_chunks([path], 4096, emu_backend, byte_ranges=[(lo, hi)]):
+            got += _chunk_records(batch)
+            chunks += 1
+        assert got == _text_records(text[lo:hi])
+        assert chunks > 3 if hi > lo else (chunks == 1 and got == [])
+        whole += got
+    assert whole == _text_records(text)
+    # a file of one long record split four ways: the shards behind the first are empty
+    long_path = str(tmp_path / "long.fastq")
+    open(long_path, "wb").write(b"@r\n" + b"A" * 3000 + b"\n+\n" + b"I" * 3000 + b"\n")
+    counts = [sum(len(b) for (b,) in read_chunks([long_path], 4096, emu_backend, byte_ranges=[r]))
+              for r in fastq_shard_ranges(long_path, 4)]
+    assert sorted(counts) == [0, 0, 0, 1]
+    gz = str(tmp_path / "in.fastq.gz")
+    with gzip.open(gz, "wb") as fh:
+        fh.write(text)
+    with pytest.raises(ValueError):
+        next(read_chunks([gz], 4096, emu_backend, byte_ranges=[(0, 100)]))
