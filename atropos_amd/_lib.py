@@ -197,9 +197,24 @@ PROTOTYPES = {
     "atr_detect_mark_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "atr_detect_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p]),
     "atr_detect_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "atr_report_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "atr_report_destroy": (None, [C.c_void_p]),
+    "atr_report_counters": (C.c_int64, [C.c_void_p]),
+    "atr_report_intervals": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "atr_report_adapters": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p]),
+    "atr_report_outputs": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p]),
+    "atr_report_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 DETECT_MAX_READ = 320                    # atr_detect_*: reads up to here (the complexity table is (len + 1)^2 doubles)
 DETECT_HDR = 8                           # detect_core.hpp: kept, distinct, invalid, overlong, then 4 x nseq counters
+
+# atr_report_*: the words of the counter block (report_core.hpp), the counting modes of a trimmer stage, the variants
+REPORT_IN_RECORDS, REPORT_IN_BASES, REPORT_WITH_ADAPTERS, REPORT_OVERFLOW = 0, 1, 2, 3
+REPORT_DEST, REPORT_DEST_BP, REPORT_TRIM, REPORT_HDR, REPORT_ADJ = 8, 16, 24, 32, 8
+REPORT_SUBSEQ, REPORT_CLIP, REPORT_MINCUT, REPORT_NEND = 0, 1, 2, 3
+REPORT_MAX_WORDS = 1 << 22                # report_core.hpp: the bound of a counter block (32 MiB)
+REPORT_VARIANTS = {"auto": 0, "lds": 1, "global": 2}
 
 FASTQ_ERR_AT, FASTQ_ERR_PLUS, FASTQ_ERR_NAME2, FASTQ_ERR_LENGTH = 1, 2, 3, 4
 DEST_KEEP, DEST_TOO_SHORT, DEST_TOO_LONG, DEST_TOO_MANY_N, DEST_TRIMMED, DEST_UNTRIMMED = range(6)
@@ -1020,6 +1035,47 @@ class HipBackend(object):
         out = np.zeros((counters.shape[0],), dtype=np.int64)
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.atr_detect_read(h, _ptr(counters), out.ctypes.data, self._stream()), "atr_detect_read")
+        return out
+
+    # -- the trim report (atr_report_*) ---------------------------------------------------------------------------
+    def report_create(self, n_adapters, max_read_len, max_errors):
+        h = C.c_void_p()
+        _check(self.lib, self.lib.atr_report_create(int(n_adapters), int(max_read_len), int(max_errors), C.byref(h)),
+               "atr_report_create")
+        return h
+
+    def report_destroy(self, h):
+        self.lib.atr_report_destroy(h)
+
+    def report_counters(self, h):
+        """A zeroed counter block (int64 tensor) for the handle's layout."""
+        words = _check(self.lib, self.lib.atr_report_counters(h), "atr_report_counters")
+        return torch.zeros((words,), dtype=torch.int64, device=self.device)
+
+    def report_intervals(self, h, records, begin0, end0, begin1, end1, mode, front, back, slot, counters):
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_report_intervals(h, _ptr(records), _ptr(begin0), _ptr(end0), _ptr(begin1), _ptr(end1),
+                                                           begin0.shape[0], int(mode), int(front), int(back), int(slot),
+                                                           _ptr(counters), self._stream()), "atr_report_intervals")
+
+    def report_adapters(self, h, data, records, took, best, which, front, default_front, begin, end, longest, weight,
+                        variant, counters):
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_report_adapters(h, _ptr(data), _ptr(records), _ptr(took), _ptr(best), _ptr(which),
+                                                          _ptr(front), int(default_front), _ptr(begin), _ptr(end),
+                                                          begin.shape[0], int(longest), int(weight), int(variant),
+                                                          _ptr(counters), self._stream()), "atr_report_adapters")
+
+    def report_outputs(self, h, records, begin, end, matched, dest, counters):
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_report_outputs(h, _ptr(records), _ptr(begin), _ptr(end), _ptr(matched), _ptr(dest),
+                                                         begin.shape[0], _ptr(counters), self._stream()), "atr_report_outputs")
+
+    def report_read(self, h, counters):
+        """The counter block as a host int64 ndarray (the one device -> host copy of a report)."""
+        out = np.zeros((counters.shape[0],), dtype=np.int64)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_report_read(h, _ptr(counters), out.ctypes.data, self._stream()), "atr_report_read")
         return out
 
 

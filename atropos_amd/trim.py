@@ -33,6 +33,7 @@ import torch
 
 from . import _lib
 from .adapters import LinkedAdapter
+from .report import SLOT_CUT, SLOT_MINCUT, SLOT_NEND, SLOT_NEXTSEQ, SLOT_QUALITY, TrimReport, check_envelope
 from .fastq import FastqBatch, RecordSource, StageClock, make_sink, open_by_extension, read_chunks
 
 DEST_MERGED = 6              # MergedReadFilter (filters.py:109-113): installed first, so a merged pair goes nowhere else
@@ -272,6 +273,19 @@ def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
     """What ``TrimPipeline.trim_file`` (one input), ``PairedTrimPipeline.trim_files`` (two inputs in lock step) and
     ``shard.sharded_trim_file`` (``byte_ranges``: a rank's part of the input) do with every chunk of
     ``fastq.read_chunks``; returns the destination counts."""
+    if not pipe.report:
+        return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, None)
+    # the report's counters: made before any output is opened (the table bound refuses here), on the device until the
+    # file is done
+    report = TrimReport(pipe, source=tuple(paths_in) if len(paths_in) == 2 else paths_in[0])
+    try:
+        return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report)
+    finally:
+        report.close()
+
+
+def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report):
+    """The chunk loop of ``_trim_stream``; ``report``: the run's TrimReport or None."""
     paired = len(paths_in) == 2
     first = pipe.p1 if paired else pipe
     merging = paired and pipe.merge_overlapping
@@ -300,6 +314,8 @@ def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
             texts = [be.fastq_emit(r.batch.data, r.batch.records, r.begin, r.end, r.ubegin, r.uend, r.dest,
                                    _lib.DEST_KEEP) for r in reads]
             counts = res.counts()
+            if report is not None:
+                report.add(res)
             if stats is not None:                             # (collect_batch's order: batches, intervals, masks)
                 post =([r.batch for r in reads] + [t for r in reads for t in (r.begin, r.end)] +
                         [t for r in reads for t in (r.ubegin, r.uend)] + [res.dest])
@@ -319,6 +335,8 @@ def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
                 totals[name] += v
         if stats is not None:
             pipe.stats_summary = stats.summary()
+        if report is not None:
+            pipe.report_summary = report.summary()
     finally:
         for obj in sinks + list(aux_files.values()) + [fh for fhs in dest_files.values() for fh in fhs]:
             obj.close()
@@ -341,8 +359,11 @@ class TrimPipeline(object):
                  quality_base=33, trim_n=False, minimum_length=None, maximum_length=None, max_n=None,
                  discard_trimmed=False, discard_untrimmed=False, op_order="CGQAW", aux=None, length_tag=None,
                  strip_suffix=(), prefix="", suffix="", zero_cap=False, outputs=None, cut_min=(), bisulfite=None,
-                 stats=None):
+                 stats=None, report=False):
         self.adapters = list(adapters)
+        # report=True: trim_file leaves the reference's summary['trim'] and input totals in self.report_summary; a
+        # caller of run() collects them with atropos_amd.report.TrimReport, which hangs its counters in here
+        self.report, self._reporter = bool(report), None
         # stats=("pre",) / ("post",) / ("pre", "post"): trim_file leaves the reference's --stats summary in
         # self.stats_summary (TrimStats)
         self.stats = _stats_modes(stats)
@@ -401,6 +422,8 @@ class TrimPipeline(object):
             raise NotImplementedError("--cut-min with linked adapters (what a LinkedMatch counts as trimmed is not the interval)")
         if self._linked and ("{name}" in self.prefix or "{name}" in self.suffix):
             raise NotImplementedError("{name} in --prefix / --suffix with linked adapters")
+        if self.report:
+            check_envelope(linked=self._linked, bisulfite=bool(self.bisulfite))
 
     # ------------------------------------------------------------------ adapter rounds
     @staticmethod
@@ -435,7 +458,11 @@ class TrimPipeline(object):
             is_front = torch.where(code == 2, best[:, 2] == 0, code == 1)
             m.sides[0] |= took & is_front
             m.sides[1] |= took & ~is_front
-        be.match_trim_batch(best.contiguous(), front, int(codes[0].item()), begin, end, active, m.matched)
+        best = best.contiguous()
+        if self._reporter is not None:                                    # Adapter.trimmed counts, once per match and round
+            self._reporter.adapter_round(batch, took, best, which, front, self._front_code(self.adapters[0]), begin, end,
+                                         source.max_len())
+        be.match_trim_batch(best, front, int(codes[0].item()), begin, end, active, m.matched)
 
     def _round_linked(self, m, active):
         """LinkedAdapter.match_to + trimmed (adapters/__init__.py:648-706) for linked adapters
@@ -531,14 +558,24 @@ class TrimPipeline(object):
         """The C, G, Q stages (interval updates without alignment)."""
         batch, begin, end = m.batch, m.begin, m.end
         be = batch.backend
+        rep = self._reporter                                              # Trimmer.trimmed_bases of the stage
         if op == "C" and (self.cut_front or self.cut_back):
+            before = (begin.clone(), end.clone()) if rep else None
             be.clip_batch(batch.records, begin, end, self.cut_front, self.cut_back)
+            if rep:
+                rep.intervals(batch, before, begin, end, _lib.REPORT_CLIP, self.cut_front, -self.cut_back, SLOT_CUT)
         elif op == "G" and self.nextseq_trim is not None:
+            before = (begin.clone(), end.clone()) if rep else None
             be.quality_trim_batch(batch.data, batch.records, begin, end, 0, int(self.nextseq_trim),
                                   self.quality_base, True)
+            if rep:
+                rep.intervals(batch, before, begin, end, _lib.REPORT_SUBSEQ, 0, 0, SLOT_NEXTSEQ)
         elif op == "Q" and self.quality_cutoff:
+            before = (begin.clone(), end.clone()) if rep else None
             be.quality_trim_batch(batch.data, batch.records, begin, end, int(self.quality_cutoff[0]),
                                   int(self.quality_cutoff[1]), self.quality_base, False)
+            if rep:
+                rep.intervals(batch, before, begin, end, _lib.REPORT_SUBSEQ, 0, 0, SLOT_QUALITY)
 
     def _filter_stage(self, m, masks=False):
         """The bisulfite cutters, --trim-n, --cut-min, then the read filters: destination byte per read (or the fail
@@ -547,8 +584,14 @@ class TrimPipeline(object):
         be = batch.backend
         if self.bisulfite:
             self._bisulfite_stage(m)
+        rep = self._reporter
         if self.trim_n:
+            before = (begin.clone(), end.clone()) if rep else None
             be.nend_trim_batch(batch.data, batch.records, begin, end, ubegin, uend)
+            if rep:
+                rep.intervals(batch, before, begin, end, _lib.REPORT_NEND, 0, 0, SLOT_NEND)
+        if (self.min_front or self.min_back) and rep:                     # (MinCutter counts what it asks clip() for)
+            rep.intervals(batch, (begin, end), begin, end, _lib.REPORT_MINCUT, self.min_front, self.min_back, SLOT_MINCUT)
         if self.min_front or self.min_back:
             # at least min_front / min_back bases gone from the two ends, whatever removed them so far: everything that
             # was cut, quality-trimmed or adapter-trimmed is in the interval (clipped[] + the matches' rsize_total)
@@ -707,8 +750,11 @@ class PairedTrimPipeline(object):
                  op_order="CGQAW", insert_args=None, correct_mismatches=None, merge_overlapping=False,
                  merge_min_overlap=0.9, merge_error_rate=0.2, aux=None, length_tag=None, strip_suffix=(), prefix="",
                  suffix="", zero_cap=False, outputs=None, cut_min=(), cut_min2=(), bisulfite=None, bisulfite2=None,
-                 stats=None):
+                 stats=None, report=False):
         self.stats = _stats_modes(stats)                                  # as TrimPipeline's: trim_files' summary
+        self.report = bool(report)                                        # as TrimPipeline's: trim_files' report_summary
+        if self.report:
+            check_envelope(aligner=aligner, merge_overlapping=bool(merge_overlapping), bisulfite=bool(bisulfite or bisulfite2))
         # {"too_short" | "too_long" | "untrimmed": (path for read 1, path for read 2)}: the filtered pairs' own files
         self.outputs = dict(outputs) if outputs else {}
         if "untrimmed" in self.outputs:
@@ -717,7 +763,7 @@ class PairedTrimPipeline(object):
                       quality_base=quality_base, trim_n=trim_n, minimum_length=minimum_length,
                       maximum_length=maximum_length, max_n=max_n, discard_trimmed=discard_trimmed,
                       discard_untrimmed=discard_untrimmed, op_order=op_order, aux=aux, length_tag=length_tag,
-                      strip_suffix=strip_suffix, prefix=prefix, suffix=suffix, zero_cap=zero_cap)
+                      strip_suffix=strip_suffix, prefix=prefix, suffix=suffix, zero_cap=zero_cap, report=report)
         self.aux = dict(aux) if aux else None
         if (aux or length_tag or strip_suffix or prefix or suffix or zero_cap) and (aligner != "adapter" or merge_overlapping):
             raise NotImplementedError("--info-file / --rest-file / --wildcard-file, read-name modifiers and --zero-cap with "
@@ -954,6 +1000,7 @@ class LegacyPairedPipeline(PairedTrimPipeline):
     def __init__(self, first):
         self.first = self.p1 = first                                      # (trim_files reads p1's filter settings)
         self.stats, self.aux, self.outputs, self.merge_overlapping = (), None, {}, False
+        self.report = first.report
 
     def run(self, batch1, batch2):
         if len(batch1) != len(batch2):
@@ -966,12 +1013,13 @@ class LegacyPairedPipeline(PairedTrimPipeline):
         return PairedTrimResult(res1, res2)
 
 
-def pipeline_from_args(argv, paired_input=False):
+def pipeline_from_args(argv, paired_input=False, report=False):
     """Build a TrimPipeline (or, when paired-end options are present, a PairedTrimPipeline) from
     the subset of ``atropos trim`` command-line options the device pipeline covers (same
     spellings and defaults as trim/cli.py:57-335, :455-530, :655-803).  Anything else raises --
     the caller then uses the per-read object path.  ``paired_input``: the reads come as pairs (-pe1 / -pe2); without
-    an option that asks for full paired-end trimming that is the reference's legacy mode (LegacyPairedPipeline)."""
+    an option that asks for full paired-end trimming that is the reference's legacy mode (LegacyPairedPipeline).
+    ``report``: the pipelines' ``report=`` (the trim report, atropos_amd.report)."""
     import argparse
     from .adapters import AdapterParser
     if isinstance(argv, str):
@@ -1113,7 +1161,7 @@ def pipeline_from_args(argv, paired_input=False):
     common = dict(times=o.times, action=action, nextseq_trim=o.nextseq_trim, quality_cutoff=qc,
                   quality_base=o.quality_base, trim_n=o.trim_n, minimum_length=o.minimum_length,
                   maximum_length=o.maximum_length, max_n=o.max_n, discard_trimmed=o.discard_trimmed,
-                  discard_untrimmed=o.discard_untrimmed, op_order=o.op_order)
+                  discard_untrimmed=o.discard_untrimmed, op_order=o.op_order, report=report)
     bis1 = bis2 = None
     if o.bisulfite:                                                       # cli.py:702-739, trim/__init__.py:497-516
         kind = o.bisulfite

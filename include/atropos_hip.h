@@ -776,6 +776,55 @@ int atr_detect_batch(const void *detect, const uint8_t *d_bytes, const atr_fastq
                      const int64_t *d_order, const uint8_t *d_rep, int64_t m, void *d_counters, void *stream);
 int atr_detect_read(const void *detect, const void *d_counters, uint64_t *out, void *stream);
 
+
+/* The trim report: summary['trim'] of the reference (RecordHandler.summarize, commands/trim/__init__.py:129-137) and
+ * the input totals, counted on the device while the trim pipeline runs.
+ *
+ * atr_report_create fixes the layout of the counter block of one read of the layout: n_adapters adapters, match
+ * lengths 0 .. max_read_len, errors 0 .. max_errors.  ATR_ERR_UNSUPPORTED beyond the table bound (64 adapters,
+ * 2^22 words).  The block itself is caller-allocated: atr_report_counters() int64 words, zeroed by the caller, resident
+ * on the device for the whole run; every call below adds to it, none reads it back.  Words: [0] input records, [1]
+ * input bases, [2] reads with an adapter, [3] matches outside the table (a caller that finds it non-zero must not
+ * trust the block), [8 + d] records sent to destination d (ATR_DEST_*, 6 = merged), [16 + d] bases of their final
+ * intervals, [24 + slot] bases trimmer `slot` counts as trimmed; from word 32 on per adapter: the base before a 3'
+ * match (A, C, G, T, anything else or none; 3 words of padding), then [front | back][length][errors] matches.
+ *
+ *   atr_report_intervals  after a trimmer stage: (d_begin0, d_end0) the intervals before it, (d_begin1, d_end1) after.
+ *                         mode ATR_REPORT_SUBSEQ counts what a read lost (Trimmer.subseq); ATR_REPORT_CLIP counts
+ *                         front + back for every read that was not empty (Trimmer.clip counts what it was asked to
+ *                         remove); ATR_REPORT_MINCUT counts what front / back still lacked at either end (MinCutter);
+ *                         ATR_REPORT_NEND is SUBSEQ for NEndTrimmer, which counts a read of nothing but N twice.
+ *   atr_report_adapters   once per adapter round, before the round's trim: d_took[i] != 0 where the round's match
+ *                         d_best[i] (8 int16: astart, astop, rstart, rstop, matches, errors) of adapter d_which[i]
+ *                         applies to the read [d_begin[i], d_end[i]); d_front / default_front as atr_match_trim_batch.
+ *                         weight 1, or 2 for the 'mask' action (AdapterCutter calls Adapter.trimmed twice per match).
+ *                         longest: upper bound of the interval lengths; ATR_ERR_UNSUPPORTED beyond max_read_len, before
+ *                         anything is launched or counted.  variant: ATR_REPORT_LDS keeps the bins of a block in LDS
+ *                         (ATR_ERR_UNSUPPORTED when the table for `longest` does not fit), ATR_REPORT_GLOBAL counts
+ *                         with global atomics, ATR_REPORT_AUTO takes LDS when it fits.
+ *   atr_report_outputs    after the filters: destinations, written bases, input totals, reads with an adapter.
+ * atr_report_read copies the block to host memory and waits for the stream. */
+#define ATR_REPORT_SUBSEQ 0
+#define ATR_REPORT_CLIP 1
+#define ATR_REPORT_MINCUT 2
+#define ATR_REPORT_NEND 3
+#define ATR_REPORT_AUTO 0
+#define ATR_REPORT_LDS 1
+#define ATR_REPORT_GLOBAL 2
+int atr_report_create(int n_adapters, int max_read_len, int max_errors, void **out);
+void atr_report_destroy(void *report);
+int64_t atr_report_counters(const void *report);
+int atr_report_intervals(const void *report, const atr_fastq_record *d_records, const int32_t *d_begin0,
+                         const int32_t *d_end0, const int32_t *d_begin1, const int32_t *d_end1, int64_t n, int mode, int front,
+                         int back, int slot, void *d_counters, void *stream);
+int atr_report_adapters(const void *report, const uint8_t *d_bytes, const atr_fastq_record *d_records, const uint8_t *d_took,
+                        const int16_t *d_best, const int64_t *d_which, const uint8_t *d_front, int default_front,
+                        const int32_t *d_begin, const int32_t *d_end, int64_t n, int longest, int weight, int variant,
+                        void *d_counters, void *stream);
+int atr_report_outputs(const void *report, const atr_fastq_record *d_records, const int32_t *d_begin, const int32_t *d_end,
+                       const uint8_t *d_matched, const uint8_t *d_dest, int64_t n, void *d_counters, void *stream);
+int atr_report_read(const void *report, const void *d_counters, int64_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
