@@ -182,6 +182,9 @@ PROTOTYPES = {
     "atr_fastq_emit_work_bytes": (C.c_size_t, [C.c_int64]),
     "atr_fastq_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "atr_fastq_emit_grouped_work_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "atr_fastq_emit_grouped": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 5),
+    "atr_demux_groups": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "atr_read_stats_bytes": (C.c_int64, [C.c_int]),
     "atr_read_stats_clear": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "atr_read_stats_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
@@ -219,6 +222,7 @@ REPORT_VARIANTS = {"auto": 0, "lds": 1, "global": 2}
 FASTQ_ERR_AT, FASTQ_ERR_PLUS, FASTQ_ERR_NAME2, FASTQ_ERR_LENGTH = 1, 2, 3, 4
 DEST_KEEP, DEST_TOO_SHORT, DEST_TOO_LONG, DEST_TOO_MANY_N, DEST_TRIMMED, DEST_UNTRIMMED = range(6)
 INT64_MAX = (1 << 63) - 1
+EMIT_MAX_GROUPS = 1024                   # atr_fastq_emit_grouped: outputs per call
 
 
 class AtroposHipError(RuntimeError):
@@ -952,6 +956,39 @@ class HipBackend(object):
             if total:
                 _check(self.lib, self.lib.atr_fastq_emit(*args, _ptr(out), self._stream()), "atr_fastq_emit")
         return out[:total]
+
+    def fastq_emit_grouped(self, data, records, begin, end, ubegin, uend, group, n_groups):
+        """atr_fastq_emit for ``n_groups`` outputs in one pass: (text, bounds) -- the formatted records with
+        ``group[r]`` (int32) == 0 first, then those of group 1 ..., input order inside a group, as one uint8 device
+        tensor, and the ``n_groups + 1`` segment boundaries as a list of ints.  Records with any other code are not
+        written."""
+        n = records.shape[0]
+        n_groups = int(n_groups)
+        if n_groups > EMIT_MAX_GROUPS:
+            raise AtroposUnsupported("atr_fastq_emit_grouped: %d outputs (at most %d)" % (n_groups, EMIT_MAX_GROUPS))
+        offsets = self.empty((max(n, 1),), torch.int64)
+        bounds = self.empty((max(n_groups, 0) + 1,), torch.int64)
+        work = self.empty((max(self.lib.atr_fastq_emit_grouped_work_bytes(n, n_groups), 16),), torch.uint8)
+        with torch.cuda.device(self.device):
+            hint = int(data.numel() // max(n, 1))
+            args = (_ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(group), n_groups, n,
+                    hint, _ptr(offsets), _ptr(bounds), _ptr(work))
+            _check(self.lib, self.lib.atr_fastq_emit_grouped(*args, None, self._stream()), "atr_fastq_emit_grouped")
+            edges = bounds.cpu().tolist()
+            out = self.empty((max(edges[-1], 1),), torch.uint8)
+            if edges[-1]:
+                _check(self.lib, self.lib.atr_fastq_emit_grouped(*args, _ptr(out), self._stream()), "atr_fastq_emit_grouped")
+        return out[:edges[-1]], edges
+
+    def demux_groups(self, dest, matched, last_which, adapter_group, n_adapters, untrimmed_group):
+        """The output code of every read of a demultiplexed run (atr_demux_groups): int32 device tensor."""
+        n = dest.shape[0]
+        group = self.empty((n,), torch.int32)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_demux_groups(_ptr(dest), _ptr(matched), _ptr(last_which), _ptr(adapter_group),
+                                                       int(n_adapters), int(untrimmed_group), n, _ptr(group), self._stream()),
+                   "atr_demux_groups")
+        return group
 
     # -- read statistics (atr_read_stats_*) ---------------------------------------------------------------------
     def read_stats_words(self, max_len):

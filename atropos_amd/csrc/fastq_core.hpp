@@ -303,6 +303,41 @@ ATR_DEV uint32_t fastq_record_bytes(const FastqRecord &rec, int kept) {
     return 1u + rec.name_len + 1u + (uint32_t)kept + 2u + fastq_name2_len(rec) + 1u + (uint32_t)kept + 1u;
 }
 
+// len bytes src -> dst by `nl` cooperating lanes (lane = 0 .. nl-1), a byte per lane and step
+ATR_DEV void lanes_copy(uint8_t *dst, const uint8_t *src, uint32_t len, int lane, int nl) {
+    for (uint32_t o = (uint32_t)lane; o < len; o += (uint32_t)nl) dst[o] = src[o];
+}
+
+// FastqFormat.format_entry (io/seqio.py:686-700): the record's text at o, fastq_record_bytes(rec, b - a)
+// bytes, written by `nl` cooperating lanes (the emulation passes 0, 1).  [a, b) is the kept interval of
+// the sequence line, [ub, ue) the part of it that AdapterCutter's 'mask' action left (a, b: no mask).
+ATR_DEV void fastq_format_record(uint8_t *o, const uint8_t *bytes, const FastqRecord &rec, int a, int b, int ub, int ue,
+                                 int lane, int nl) {
+    const uint32_t kept = (uint32_t)(b - a);
+    if (lane == 0) o[0] = '@';
+    lanes_copy(o + 1, bytes + rec.name_off, rec.name_len, lane, nl);
+    o += 1 + rec.name_len;
+    if (lane == 0) o[0] = '\n';
+    o += 1;
+    if (ub > a || ue < b) {
+        for (uint32_t k = (uint32_t)lane; k < kept; k += (uint32_t)nl) {
+            const int pos = a + (int)k;
+            o[k] = (pos >= ub && pos < ue) ? bytes[rec.seq_off + pos] : (uint8_t)'N';
+        }
+    } else {
+        lanes_copy(o, bytes + rec.seq_off + a, kept, lane, nl);
+    }
+    o += kept;
+    if (lane == 0) { o[0] = '\n'; o[1] = '+'; }
+    o += 2;
+    if (rec.flags & 1u) { lanes_copy(o, bytes + fastq_name2_off(rec), fastq_name2_len(rec), lane, nl); o += fastq_name2_len(rec); }
+    if (lane == 0) o[0] = '\n';
+    o += 1;
+    lanes_copy(o, bytes + rec.qual_off + a, kept, lane, nl);
+    o += kept;
+    if (lane == 0) o[0] = '\n';
+}
+
 // ---- MergeOverlapping (commands/trim/modifiers.py:864-931) ---------------------------------
 // al = the record of Aligner(reverse_complement(read2), error_rate, flags).locate(read1):
 // (r2_start, r2_stop, r1_start, r1_stop, matches, errors), refstop -1 = None (or a pair that was

@@ -21,6 +21,7 @@
 #include "locate_core.hpp"
 #include "fastq_core.hpp"
 #include "misc_core.hpp"
+#include "demux_core.hpp"
 
 #include "pack_fast.hpp"
 
@@ -429,10 +430,6 @@ __global__ void emit_total_kernel(const uint32_t *__restrict__ sizes, long long 
     offsets[n] = n ? offsets[n - 1] + (long long)sizes[n - 1] : 0;
 }
 
-__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *src, uint32_t len, int lane) {
-    for (uint32_t o = (uint32_t)lane; o < len; o += 64u) dst[o] = src[o];
-}
-
 // One wave formats 64 consecutive records, one after the other, a byte per lane.
 __global__ __launch_bounds__(256) void emit_kernel(const uint8_t *__restrict__ bytes,
                                                    const FastqRecord *__restrict__ records,
@@ -448,33 +445,8 @@ __global__ __launch_bounds__(256) void emit_kernel(const uint8_t *__restrict__ b
     for (int i = 0; i < cnt; ++i) {
         const long long r = r0 + i;                               // wave-uniform
         if (dest && dest[r] != which) continue;
-        const FastqRecord rec = records[r];
         const int a = begin[r], b = max(a, end[r]);
-        const uint32_t kept = (uint32_t)(b - a);
-        uint8_t *o = out + offsets[r];
-        if (lane == 0) o[0] = '@';
-        wave_copy(o + 1, bytes + rec.name_off, rec.name_len, lane);
-        o += 1 + rec.name_len;
-        if (lane == 0) o[0] = '\n';
-        o += 1;
-        if (ubegin) {
-            const int ub = ubegin[r], ue = uend[r];
-            for (uint32_t k = (uint32_t)lane; k < kept; k += 64u) {
-                const int pos = a + (int)k;
-                o[k] = (pos >= ub && pos < ue) ? bytes[rec.seq_off + pos] : (uint8_t)'N';
-            }
-        } else {
-            wave_copy(o, bytes + rec.seq_off + a, kept, lane);
-        }
-        o += kept;
-        if (lane == 0) { o[0] = '\n'; o[1] = '+'; }
-        o += 2;
-        if (rec.flags & 1u) { wave_copy(o, bytes + fastq_name2_off(rec), fastq_name2_len(rec), lane); o += fastq_name2_len(rec); }
-        if (lane == 0) o[0] = '\n';
-        o += 1;
-        wave_copy(o, bytes + rec.qual_off + a, kept, lane);
-        o += kept;
-        if (lane == 0) o[0] = '\n';
+        fastq_format_record(out + offsets[r], bytes, records[r], a, b, ubegin ? ubegin[r] : a, uend ? uend[r] : b, lane, 64);
     }
 }
 
@@ -565,29 +537,9 @@ __global__ __launch_bounds__(64) void emit_staged_kernel(const uint8_t *__restri
         for (int i = 0; i < cnt; ++i) {
             const long long ri = r0 + i;
             if (dest && dest[ri] != which) continue;
-            const FastqRecord rc = records[ri];
             const int ai = begin[ri], bi = max(ai, end[ri]);
-            const uint32_t kept = (uint32_t)(bi - ai);
-            uint8_t *o = out + offsets[ri];
-            if (lane == 0) o[0] = '@';
-            wave_copy(o + 1, bytes + rc.name_off, rc.name_len, lane);
-            o += 1 + rc.name_len;
-            if (lane == 0) o[0] = '\n';
-            o += 1;
-            const int ubi = ubegin ? ubegin[ri] : ai, uei = uend ? uend[ri] : bi;
-            for (uint32_t k = (uint32_t)lane; k < kept; k += 64u) {
-                const int pos = ai + (int)k;
-                o[k] = (pos >= ubi && pos < uei) ? bytes[rc.seq_off + pos] : (uint8_t)'N';
-            }
-            o += kept;
-            if (lane == 0) { o[0] = '\n'; o[1] = '+'; }
-            o += 2;
-            if (rc.flags & 1u) { wave_copy(o, bytes + fastq_name2_off(rc), fastq_name2_len(rc), lane); o += fastq_name2_len(rc); }
-            if (lane == 0) o[0] = '\n';
-            o += 1;
-            wave_copy(o, bytes + rc.qual_off + ai, kept, lane);
-            o += kept;
-            if (lane == 0) o[0] = '\n';
+            fastq_format_record(out + offsets[ri], bytes, records[ri], ai, bi, ubegin ? ubegin[ri] : ai, uend ? uend[ri] : bi,
+                                lane, 64);
         }
         return;
     }
@@ -643,6 +595,138 @@ __global__ __launch_bounds__(64) void emit_staged_kernel(const uint8_t *__restri
             }
         }
     }
+}
+
+// ---- grouped formatter ------------------------------------------------------------------
+// atr_fastq_emit_grouped: the records of group 0 first, then group 1's ..., input order inside a group -- a
+// stable partition by group with a byte-weighted prefix, in one pass over the records per call:
+//   sizing:  group_hist_kernel     bytes per (group, block of 256 records), summed in LDS
+//            launch_scan           exclusive 64-bit scan of that matrix, group-major: entry (g, b) becomes the
+//                                  position of the first byte block b adds to group g
+//            group_offsets_kernel  the position of every record: matrix entry + the bytes the earlier records
+//                                  of its block add to its group
+//   writing: emit_grouped_kernel   every wave formats its 64 records, each at its position
+// No global atomics: the positions do not depend on the launch shape or on timing.
+constexpr int GRP_BLOCK = 256;
+
+__device__ __forceinline__ uint32_t grouped_load(const FastqRecord *records, const int32_t *begin, const int32_t *end,
+                                                 const int32_t *group, int n_groups, long long r, long long n, int &g) {
+    g = -1;
+    if (r >= n) return 0u;
+    g = group[r];
+    return demux_record_bytes(records[r], begin[r], end[r], g, n_groups);
+}
+
+// LDS: n_groups uint32
+__global__ __launch_bounds__(GRP_BLOCK) void group_hist_kernel(const FastqRecord *__restrict__ records,
+                                                               const int32_t *__restrict__ begin,
+                                                               const int32_t *__restrict__ end,
+                                                               const int32_t *__restrict__ group, int n_groups, long long n,
+                                                               long long nb, uint32_t *__restrict__ hist) {
+    extern __shared__ uint32_t s_hist[];
+    for (int i = threadIdx.x; i < n_groups; i += GRP_BLOCK) s_hist[i] = 0u;
+    __syncthreads();
+    int g;
+    const uint32_t s = grouped_load(records, begin, end, group, n_groups, (long long)blockIdx.x * GRP_BLOCK + threadIdx.x, n, g);
+    if (g >= 0) atomicAdd(&s_hist[g], s);                       // (integer sums in LDS: the order does not show)
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_groups; i += GRP_BLOCK) hist[(long long)i * nb + blockIdx.x] = s_hist[i];
+}
+
+// LDS: (GRP_BLOCK / 64) x n_groups uint32 -- what every wave of the block adds to every group
+__global__ __launch_bounds__(GRP_BLOCK) void group_offsets_kernel(const FastqRecord *__restrict__ records,
+                                                                  const int32_t *__restrict__ begin,
+                                                                  const int32_t *__restrict__ end,
+                                                                  const int32_t *__restrict__ group, int n_groups, long long n,
+                                                                  long long nb, const long long *__restrict__ base,
+                                                                  long long *__restrict__ offsets,
+                                                                  long long *__restrict__ group_offsets) {
+    extern __shared__ uint32_t s_wave[];
+    for (int i = threadIdx.x; i < (GRP_BLOCK / 64) * n_groups; i += GRP_BLOCK) s_wave[i] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long r = (long long)blockIdx.x * GRP_BLOCK + threadIdx.x;
+    int g;
+    const uint32_t s = grouped_load(records, begin, end, group, n_groups, r, n, g);
+    // the distinct groups of the wave, one after the other: the lanes of the leader's group take the prefix of
+    // their sizes in lane order (= input order), the leader notes the group's total
+    uint32_t before = 0u;
+    unsigned long long todo = __ballot(g >= 0);
+    while (todo) {                                              // wave-uniform
+        const int leader = __ffsll((long long)todo) - 1;
+        const int lg = __shfl(g, leader, 64);
+        const bool mine = g == lg;
+        uint32_t x = mine ? s : 0u;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t y = __shfl_up(x, off, 64);
+            if (lane >= off) x += y;
+        }
+        if (mine) before = x - s;
+        const uint32_t total = __shfl(x, 63, 64);
+        if (lane == leader) s_wave[wave * n_groups + lg] = total;
+        todo &= ~__ballot(mine);
+    }
+    __syncthreads();
+    if (r < n) {
+        long long pos = -1;                                     // a record that is not written has no position
+        if (g >= 0) {
+            pos = base[(long long)g * nb + blockIdx.x] + (long long)before;
+            for (int w = 0; w < wave; ++w) pos += (long long)s_wave[w * n_groups + g];
+        }
+        offsets[r] = pos;
+    }
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n_groups; i += GRP_BLOCK) group_offsets[i] = base[(long long)i * nb];
+}
+
+// One wave formats 64 consecutive records: every lane fetches the state of one, then the wave writes them one
+// after the other with fastq_format_record, a byte per lane (neighbours go to different places of the buffer,
+// so there is no output span to stage as emit_staged_kernel does).
+__global__ __launch_bounds__(256) void emit_grouped_kernel(const uint8_t *__restrict__ bytes,
+                                                           const FastqRecord *__restrict__ records,
+                                                           const int32_t *__restrict__ begin, const int32_t *__restrict__ end,
+                                                           const int32_t *__restrict__ ubegin, const int32_t *__restrict__ uend,
+                                                           const int32_t *__restrict__ group, int n_groups, long long n,
+                                                           const long long *__restrict__ offsets, uint8_t *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long long r = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + lane;
+    FastqRecord rec = {0, 0, 0, 0, 0, 0, 0, 0};
+    int a = 0, b = 0, ub = 0, ue = 0;
+    long long off = -1;
+    if (r < n) {
+        const int g = group[r];
+        if (g >= 0 && g < n_groups) {
+            rec = records[r];
+            a = begin[r];
+            b = max(a, end[r]);
+            ub = ubegin ? ubegin[r] : a;
+            ue = uend ? uend[r] : b;
+            off = offsets[r];
+        }
+    }
+    unsigned long long todo = __ballot(off >= 0);
+    while (todo) {                                              // wave-uniform
+        const int i = __ffsll((long long)todo) - 1;
+        todo &= todo - 1ull;
+        FastqRecord rc;
+        rc.name_off = __shfl(rec.name_off, i, 64); rc.name_len = __shfl(rec.name_len, i, 64);
+        rc.seq_off = __shfl(rec.seq_off, i, 64); rc.seq_len = __shfl(rec.seq_len, i, 64);
+        rc.qual_off = __shfl(rec.qual_off, i, 64); rc.qual_len = __shfl(rec.qual_len, i, 64);
+        rc.flags = __shfl(rec.flags, i, 64); rc.reserved = __shfl(rec.reserved, i, 64);
+        const long long oi = __shfl(off, i, 64);
+        fastq_format_record(out + oi, bytes, rc, __shfl(a, i, 64), __shfl(b, i, 64), __shfl(ub, i, 64), __shfl(ue, i, 64),
+                            lane, 64);
+    }
+}
+
+__global__ __launch_bounds__(256) void demux_groups_kernel(const uint8_t *__restrict__ dest, const uint8_t *__restrict__ matched,
+                                                           const long long *__restrict__ which,
+                                                           const int32_t *__restrict__ adapter_group, int n_adapters,
+                                                           int untrimmed_group, long long n, int32_t *__restrict__ group) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    group[r] = demux_group_one(dest[r], matched[r] != 0, which[r], adapter_group, n_adapters, untrimmed_group);
 }
 
 // ------------------------------------------------------------------------- MergeOverlapping
@@ -962,6 +1046,61 @@ int atr_fastq_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, co
                        (const FastqRecord *)d_records, d_begin, d_end, d_unmasked_begin, d_unmasked_end, d_dest, dest,
                        (long long)n, (const long long *)d_offsets, d_out);
     return launched("emit_kernel launch");
+}
+
+// work layout: [hist u32 x n_groups * nb][base i64 x n_groups * nb][sums u64 x scan_blocks(n_groups * nb)],
+// nb = blocks of GRP_BLOCK records
+size_t atr_fastq_emit_grouped_work_bytes(int64_t n, int n_groups) {
+    if (n < 0 || n_groups < 1 || n_groups > ATR_EMIT_MAX_GROUPS) return 0;
+    const long long cells = (long long)n_groups * ((n + GRP_BLOCK - 1) / GRP_BLOCK);
+    return align256((size_t)cells * 4) + align256((size_t)cells * 8) + align256((size_t)scan_blocks(cells) * 8) + 256;
+}
+
+int atr_fastq_emit_grouped(const uint8_t *d_bytes, const atr_fastq_record *d_records, const int32_t *d_begin,
+                           const int32_t *d_end, const int32_t *d_unmasked_begin, const int32_t *d_unmasked_end,
+                           const int32_t *d_group, int n_groups, int64_t n, int record_bytes_hint, int64_t *d_offsets,
+                           int64_t *d_group_offsets, void *d_work, uint8_t *d_out, void *stream) {
+    (void)record_bytes_hint;
+    if (n_groups > ATR_EMIT_MAX_GROUPS) return ATR_ERR_UNSUPPORTED;
+    if (n < 0 || n_groups < 1 || !d_group_offsets || ((d_unmasked_begin == nullptr) != (d_unmasked_end == nullptr)))
+        return ATR_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        if (!d_out) {
+            hipError_t me = hipMemsetAsync(d_group_offsets, 0, (size_t)(n_groups + 1) * 8, st);
+            if (me != hipSuccess) return hip_fail(me, "hipMemsetAsync");
+        }
+        return ATR_OK;
+    }
+    if (!d_bytes || !d_records || !d_begin || !d_end || !d_group || !d_offsets || !d_work) return ATR_ERR_INVALID;
+    const FastqRecord *records = (const FastqRecord *)d_records;
+    if (!d_out) {
+        const long long nb = (n + GRP_BLOCK - 1) / GRP_BLOCK, cells = (long long)n_groups * nb;
+        uint32_t *hist = (uint32_t *)d_work;
+        long long *base = (long long *)((char *)d_work + align256((size_t)cells * 4));
+        unsigned long long *sums = (unsigned long long *)((char *)base + align256((size_t)cells * 8));
+        hipLaunchKernelGGL(group_hist_kernel, dim3((unsigned)nb), dim3(GRP_BLOCK), (size_t)n_groups * 4, st, records, d_begin,
+                           d_end, d_group, n_groups, (long long)n, nb, hist);
+        launch_scan(hist, cells, base, sums, (long long *)d_group_offsets + n_groups, st);
+        hipLaunchKernelGGL(group_offsets_kernel, dim3((unsigned)nb), dim3(GRP_BLOCK), (size_t)(GRP_BLOCK / 64) * n_groups * 4, st,
+                           records, d_begin, d_end, d_group, n_groups, (long long)n, nb, (const long long *)base,
+                           (long long *)d_offsets, (long long *)d_group_offsets);
+        return launched("fastq grouped emit sizes launch");
+    }
+    hipLaunchKernelGGL(emit_grouped_kernel, dim3(grid256(n)), dim3(256), 0, st, d_bytes, records, d_begin, d_end,
+                       d_unmasked_begin, d_unmasked_end, d_group, n_groups, (long long)n, (const long long *)d_offsets, d_out);
+    return launched("emit_grouped_kernel launch");
+}
+
+int atr_demux_groups(const uint8_t *d_dest, const uint8_t *d_matched, const int64_t *d_last_which,
+                     const int32_t *d_adapter_group, int n_adapters, int untrimmed_group, int64_t n, int32_t *d_group,
+                     void *stream) {
+    if (n < 0 || n_adapters < 0) return ATR_ERR_INVALID;
+    if (n == 0) return ATR_OK;
+    if (!d_dest || !d_matched || !d_last_which || !d_group) return ATR_ERR_INVALID;
+    hipLaunchKernelGGL(demux_groups_kernel, dim3(grid256(n)), dim3(256), 0, (hipStream_t)stream, d_dest, d_matched,
+                       (const long long *)d_last_which, d_adapter_group, n_adapters, untrimmed_group, (long long)n, d_group);
+    return launched("demux_groups_kernel launch");
 }
 
 size_t atr_merge_work_bytes(int64_t n) { return atr_fastq_emit_work_bytes(n); }

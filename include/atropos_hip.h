@@ -662,6 +662,32 @@ int atr_fastq_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, co
                    const uint8_t *d_dest, int dest, int64_t n, int record_bytes_hint, int64_t *d_offsets, void *d_work,
                    uint8_t *d_out, void *stream);
 
+/* Demultiplexing (`{name}` in the output path; commands/trim/writers.py:119-154): atr_fastq_emit for many
+ * outputs in one pass.  d_group[r] (device int32) is the output of record r, 0 .. n_groups-1; any other value: the
+ * record is not written.  The records of output 0 come first in d_out, then those of output 1 ...; inside an
+ * output the records keep their input order.  First call with d_out == NULL: d_offsets[n] (device int64) receives
+ * the byte position of every written record in d_out (-1 for the others) and d_group_offsets[n_groups + 1] the
+ * boundaries of the outputs' segments (d_group_offsets[n_groups] = total bytes); second call with d_out of that
+ * many bytes writes the text, every record by the code atr_fastq_emit formats it with.  d_work: scratch of
+ * atr_fastq_emit_grouped_work_bytes(n, n_groups) bytes (0: n or n_groups out of range).  record_bytes_hint: as for
+ * atr_fastq_emit; the one writing kernel there is takes no hint yet.  The positions are made without global
+ * atomics: equal inputs give equal bytes.
+ * ATR_ERR_UNSUPPORTED: n_groups > ATR_EMIT_MAX_GROUPS, before anything is launched. */
+#define ATR_EMIT_MAX_GROUPS 1024
+size_t atr_fastq_emit_grouped_work_bytes(int64_t n, int n_groups);
+int atr_fastq_emit_grouped(const uint8_t *d_bytes, const atr_fastq_record *d_records, const int32_t *d_begin,
+                           const int32_t *d_end, const int32_t *d_unmasked_begin, const int32_t *d_unmasked_end,
+                           const int32_t *d_group, int n_groups, int64_t n, int record_bytes_hint, int64_t *d_offsets,
+                           int64_t *d_group_offsets, void *d_work, uint8_t *d_out, void *stream);
+
+/* The output of every read of a demultiplexed run (Formatters.format, writers.py:138-154): d_group[r] =
+ * the output of the adapter of the read's last match (d_adapter_group[d_last_which[r]], device int32 x n_adapters;
+ * NULL: the adapter's index) for a read with d_dest[r] == ATR_DEST_KEEP and d_matched[r]; untrimmed_group for a
+ * kept read without a match and for ATR_DEST_UNTRIMMED (-1: there is no untrimmed output); -1 for every other read. */
+int atr_demux_groups(const uint8_t *d_dest, const uint8_t *d_matched, const int64_t *d_last_which,
+                     const int32_t *d_adapter_group, int n_adapters, int untrimmed_group, int64_t n, int32_t *d_group,
+                     void *stream);
+
 /* MergeOverlapping.__call__ after the alignment (commands/trim/modifiers.py:864-931), two calls:
  *
  * atr_merge_plan_batch: d_align = one record per pair of Aligner(reverse_complement(read2), error_rate,
