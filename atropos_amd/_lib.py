@@ -208,7 +208,13 @@ PROTOTYPES = {
                                       C.c_void_p, C.c_void_p]),
     "atr_report_outputs": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p]),
     "atr_report_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "atr_gzip_bound": (C.c_int64, [C.c_int64]),
+    "atr_gzip_work_bytes": (C.c_size_t, [C.c_int64]),
+    "atr_gzip_eof": (C.c_int, [C.c_void_p]),
+    "atr_gzip_blocks": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
 }
+GZIP_BLOCK = 65280                       # atr_gzip_blocks: bytes of text per BGZF member
+GZIP_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")  # atr_gzip_eof
 DETECT_MAX_READ = 320                    # atr_detect_*: reads up to here (the complexity table is (len + 1)^2 doubles)
 DETECT_HDR = 8                           # detect_core.hpp: kept, distinct, invalid, overlong, then 4 x nseq counters
 
@@ -989,6 +995,28 @@ class HipBackend(object):
                                                        int(n_adapters), int(untrimmed_group), n, _ptr(group), self._stream()),
                    "atr_demux_groups")
         return group
+
+    # -- .gz output on the device (atr_gzip_*) ------------------------------------------------------------------
+    def gzip_bound(self, nbytes):
+        return _check(self.lib, self.lib.atr_gzip_bound(int(nbytes)), "atr_gzip_bound")
+
+    def gzip_blocks(self, text, offsets=False):
+        """``text`` (uint8 device tensor) as a stream of BGZF members, one per ``GZIP_BLOCK`` bytes: (stream, total) --
+        a uint8 device tensor whose first ``total`` bytes are the members in input order -- and with ``offsets`` also
+        the int64 device tensor of the member starts followed by the total.  Reading ``total`` waits for the kernels."""
+        n = int(text.numel())
+        if not text.is_contiguous():
+            text = text.contiguous()
+        cap = self.gzip_bound(n)
+        out = self.empty((max(cap, 1),), torch.uint8)
+        total = self.empty((1,), torch.int64)
+        starts = self.empty(((n + GZIP_BLOCK - 1) // GZIP_BLOCK + 1,), torch.int64) if offsets else None
+        work = self.empty((max(self.lib.atr_gzip_work_bytes(n), 16),), torch.uint8)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_gzip_blocks(_ptr(text), n, _ptr(out), cap, _ptr(total), _ptr(starts), _ptr(work),
+                                                      self._stream()), "atr_gzip_blocks")
+            size = int(total.item())
+        return (out, size, starts) if offsets else (out, size)
 
     # -- read statistics (atr_read_stats_*) ---------------------------------------------------------------------
     def read_stats_words(self, max_len):

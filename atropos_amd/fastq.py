@@ -772,7 +772,9 @@ class PartSink(object):
 class CompressedSink(object):
     """The output through a host compressor (``.gz`` / ``.bz2`` / ``.xz`` by extension, as the reference's xopen):
     a writer thread takes the chunks in order, so that the GPU goes on with the next chunk while one is compressed.
-    One host thread compresses -- it sets the pace of the whole run (pigz-style parallel blocks: the caller's pipe)."""
+    One host thread compresses -- it sets the pace of the whole run.  This is the default for every compressed
+    output, and the only path for ``.bz2`` / ``.xz``, side files and demultiplexed outputs; for the main ``.gz``
+    outputs ``make_sink(..., device_gzip=True)`` compresses on the GPU instead (``DeviceGzipSink``)."""
 
     def __init__(self, path, clock=None):
         name = str(path)
@@ -806,6 +808,35 @@ class CompressedSink(object):
             self.fh.close()
 
 
+class DeviceGzipSink(object):
+    """``.gz`` output compressed on the device: every chunk of text becomes a stream of BGZF members
+    (``backend.gzip_blocks``: a gzip member per 65 280 bytes, dynamic Huffman over an LZ77 parse) on the caller's
+    stream, and the compressed tensor -- a half to a quarter of the text -- goes the way plain text goes: the
+    ``FastqSink`` machinery (page-locked staging buffers, copy stream, writer thread).  ``write`` reads the
+    compressed length, so the text has been consumed when it returns; the compressed tensor is kept alive by
+    the sink until its copy has landed.  An empty chunk writes nothing; ``close`` appends the 28-byte BGZF
+    end-of-file member, which alone is the file of a run that keeps no read.  The file's bytes depend on the
+    text and on where the chunks end, not on time or scheduling; decompressed it is the plain file."""
+
+    def __init__(self, path, capacity, backend=None, clock=None, keep=False):
+        self.be = backend or _lib.get_backend()
+        # compressed text is rarely more than half the text; what is goes out in pieces (FastqSink.write)
+        self.sink = FastqSink(path, int(capacity) // 2 + (1 << 20), self.be, clock, keep=keep)
+
+    def write(self, text):
+        if not int(text.numel()):
+            return
+        stream, total = self.be.gzip_blocks(text)
+        self.sink.write(stream[:total])
+
+    def close(self):
+        try:
+            eof = torch.frombuffer(bytearray(_lib.GZIP_EOF), dtype=torch.uint8)
+            self.sink.write(eof.to(self.be.device))
+        finally:
+            self.sink.close()
+
+
 def open_by_extension(path):
     """A binary file object for writing; ``.gz`` / ``.bz2`` / ``.xz`` compress (the reference's xopen does so for EVERY
     output, the side files -- too-short, untrimmed, info, rest, wildcard -- included)."""
@@ -822,8 +853,15 @@ def open_by_extension(path):
     return open(name, "wb")
 
 
-def make_sink(path, parts, capacity, backend=None, clock=None, keep=False):
-    """One file, or ``parts`` > 1 part files (PartSink); a compressed file by its extension (CompressedSink)."""
+def make_sink(path, parts, capacity, backend=None, clock=None, keep=False, device_gzip=False):
+    """One file, or ``parts`` > 1 part files (PartSink); a compressed file by its extension (CompressedSink).
+    ``device_gzip``: a ``.gz`` file compressed on the GPU (DeviceGzipSink); any other path is a ValueError with it."""
+    if device_gzip:
+        if not str(path).endswith(".gz"):
+            raise ValueError("device_gzip: the output path must end in .gz (%r)" % str(path))
+        if parts and int(parts) > 1:
+            raise ValueError("part files of a compressed output are not provided")
+        return DeviceGzipSink(path, capacity, backend, clock, keep)
     if str(path).endswith((".gz", ".bz2", ".xz")):
         if parts and int(parts) > 1:
             raise ValueError("part files of a compressed output are not provided")

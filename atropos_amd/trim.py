@@ -288,23 +288,42 @@ def _run_stages(pipes, mates, insert_stage=None):
     return found
 
 
-def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out=None, byte_ranges=None):
+def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out=None, byte_ranges=None,
+                 device_gzip=False):
     """What ``TrimPipeline.trim_file`` (one input), ``PairedTrimPipeline.trim_files`` (two inputs in lock step) and
     ``shard.sharded_trim_file`` (``byte_ranges``: a rank's part of the input) do with every chunk of
     ``fastq.read_chunks``; returns the destination counts."""
+    if device_gzip:
+        # the main outputs compressed on the device (fastq.DeviceGzipSink); refused before anything is opened
+        if output_parts and int(output_parts) > 1:
+            raise NotImplementedError("device_gzip with part files (output_parts > 1)")
+        if pipe_demultiplexes(pipe, paths_out, merged_out):
+            raise NotImplementedError("device_gzip with demultiplexed outputs ({name} in the output path)")
+        for p in list(paths_out) + ([merged_out] if merged_out is not None else []):
+            if not str(p).endswith(".gz"):
+                raise ValueError("device_gzip: the output path must end in .gz (%r)" % str(p))
     if not pipe.report:
-        return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, None)
+        return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, None,
+                            device_gzip)
     # the report's counters: made before any output is opened (the table bound refuses here), on the device until the
     # file is done
     report = TrimReport(pipe, source=tuple(paths_in) if len(paths_in) == 2 else paths_in[0])
     try:
-        return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report)
+        return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report,
+                            device_gzip)
     finally:
         report.close()
 
 
-def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report):
-    """The chunk loop of ``_trim_stream``; ``report``: the run's TrimReport or None."""
+def pipe_demultiplexes(pipe, paths_out, merged_out=None):
+    return bool(getattr(pipe, "demultiplex", False)) or any(
+        p is not None and "{name}" in str(p) for p in list(paths_out) + [merged_out])
+
+
+def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report,
+                 device_gzip=False):
+    """The chunk loop of ``_trim_stream``; ``report``: the run's TrimReport or None; ``device_gzip``: the main
+    outputs and the merged output through ``fastq.DeviceGzipSink`` (side files stay on the host path)."""
     paired = len(paths_in) == 2
     first = pipe.p1 if paired else pipe
     merging = paired and pipe.merge_overlapping
@@ -320,7 +339,8 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
         demux_paths = pipe._demux_paths(paths_out[0])
         pipe.demux_counts = {}
     else:
-        sinks = [make_sink(p, output_parts, chunk_bytes + (64 << 20) + 32, be, clock, keep=keep_output) for p in paths_out]
+        sinks = [make_sink(p, output_parts, chunk_bytes + (64 << 20) + 32, be, clock, keep=keep_output, device_gzip=device_gzip)
+                 for p in paths_out]
     aux_files = {kind: open_by_extension(path) for kind, path in (pipe.aux or {}).items()}
     dest_codes = {name: code for code, name in DEST_NAMES.items()}
     dest_files = {dest_codes[kind]: [open_by_extension(p) for p in (paths if paired else (paths,))]
@@ -330,7 +350,8 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
         totals["merged"] = 0
         if merged_out is not None:
             # a merged record is at most its two input records, and each input chunk may carry up to 64 MB over
-            sinks.append(make_sink(merged_out, output_parts, 2 * (chunk_bytes + (64 << 20)) + 32, be, clock, keep=keep_output))
+            sinks.append(make_sink(merged_out, output_parts, 2 * (chunk_bytes + (64 << 20)) + 32, be, clock, keep=keep_output,
+                                   device_gzip=device_gzip))
     stats = TrimStats(pipe.stats, paired, first.quality_base) if pipe.stats else None
     try:
         for batches in read_chunks(paths_in, chunk_bytes, be, clock, byte_ranges):
@@ -782,7 +803,7 @@ class TrimPipeline(object):
         batch, _ = FastqBatch.from_bytes(data, final=True)
         return self.run(batch).text(which)
 
-    def trim_file(self, path_in, path_out, chunk_bytes=256 << 20, keep_output=False, output_parts=1):
+    def trim_file(self, path_in, path_out, chunk_bytes=256 << 20, keep_output=False, output_parts=1, device_gzip=False):
         """Stream a FASTQ file through the GPU in chunks of whole records; returns the
         destination counts.  (Plain files; compressed input is the caller's business.)
         Host side: ``fastq.read_chunks`` (the one chunk loop, over ``ChunkedFastqReader``) / ``FastqSink`` (page-locked staging buffers, threaded
@@ -798,9 +819,15 @@ class TrimPipeline(object):
         every read that is kept goes to the file named after the adapter of its last match, a read without a match
         to the file of the name ``unknown`` or to --untrimmed-output (nowhere with --discard-untrimmed); a name
         without reads leaves no file.  The records per name are left in ``self.demux_counts``.  Single-end only, as
-        in the reference; linked adapters, ``report=True`` and part files are refused with it."""
+        in the reference; linked adapters, ``report=True`` and part files are refused with it.
+
+        ``device_gzip``: ``path_out`` ends in ``.gz`` and is compressed on the GPU (``fastq.DeviceGzipSink``: BGZF
+        members, any gzip reader takes them) instead of by one host thread; the decompressed bytes are the same.
+        Side files stay on the host path; with ``{name}`` or ``output_parts`` > 1 it is a NotImplementedError."""
+        if device_gzip and ("{name}" in path_out or self.demultiplex):
+            raise NotImplementedError("device_gzip with demultiplexed outputs ({name} in the output path)")
         if "{name}" not in path_out and not self.demultiplex:
-            return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts)
+            return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts, device_gzip=device_gzip)
         if "{name}" not in path_out:
             raise ValueError("a demultiplexing pipeline needs {name} in the output path")
         if output_parts and int(output_parts) > 1:
@@ -1090,15 +1117,20 @@ class PairedTrimPipeline(object):
             dest = torch.where(merged, torch.full_like(dest, DEST_MERGED), dest)
         return PairedTrimResult(self.p1._result(mates[0], dest), self.p2._result(mates[1], dest), merged_text)
 
-    def trim_files(self, in1, in2, out1, out2, chunk_bytes=128 << 20, merged_out=None, keep_output=False, output_parts=1):
+    def trim_files(self, in1, in2, out1, out2, chunk_bytes=128 << 20, merged_out=None, keep_output=False, output_parts=1,
+                   device_gzip=False):
         """Stream two FASTQ files through the GPU in lock step (chunks of whole records, the
         same number from each file); returns the destination counts.  ``merged_out``: the
         --merged-output file (without it merged reads are dropped, as by the reference).
         ``output_parts`` > 1: every output as that many part files (``TrimPipeline.trim_file``); part i of
-        ``out1`` and part i of ``out2`` hold the same pairs in the same order."""
+        ``out1`` and part i of ``out2`` hold the same pairs in the same order.  ``device_gzip``: the outputs
+        (all ending in ``.gz``) are compressed on the GPU, as in ``TrimPipeline.trim_file``."""
+        if device_gzip and any(p is not None and "{name}" in str(p) for p in (out1, out2, merged_out)):
+            raise NotImplementedError("device_gzip with demultiplexed outputs ({name} in the output path)")
         if any(p is not None and "{name}" in str(p) for p in (out1, out2, merged_out)):
             raise ValueError("Demultiplexing not supported for paired-end files, yet.")        # trim/cli.py:769-771
-        return _trim_stream(self, [in1, in2], [out1, out2], chunk_bytes, keep_output, output_parts, merged_out)
+        return _trim_stream(self, [in1, in2], [out1, out2], chunk_bytes, keep_output, output_parts, merged_out,
+                            device_gzip=device_gzip)
 
     def trim_bytes(self, data1, data2, which=_lib.DEST_KEEP):
         """Two FASTQ texts in (same number of records), the two trimmed texts out."""

@@ -851,6 +851,26 @@ int atr_report_outputs(const void *report, const atr_fastq_record *d_records, co
                        const uint8_t *d_matched, const uint8_t *d_dest, int64_t n, void *d_counters, void *stream);
 int atr_report_read(const void *report, const void *d_counters, int64_t *out, void *stream);
 
+/* ---- .gz output compressed on the device (gzip_kernels.hip, deflate_core.hpp) ----------------------------------------
+ * atr_gzip_blocks turns n_bytes of text in device memory into one contiguous stream of BGZF members in input order:
+ * a gzip member with the 6-byte 'BC' extra field (BSIZE = member size - 1) per ATR_GZIP_BLOCK bytes of text, the
+ * last one possibly shorter, none for n_bytes == 0.  Each member holds one dynamic-Huffman deflate block over an
+ * LZ77 parse (window 32 KiB), or a stored block where that would not be smaller: a member is at most its input plus
+ * 31 bytes.  mtime 0, XFL 0, OS 255: the stream's bytes are a function of the text alone.  Concatenated members
+ * are a valid gzip file; a BGZF file ends with the 28-byte member of atr_gzip_eof.
+ *   atr_gzip_bound(n_bytes)       capacity the compacted output needs (ATR_ERR_INVALID for n_bytes < 0)
+ *   atr_gzip_work_bytes(n_bytes)  bytes of d_work (0 for n_bytes < 0)
+ *   d_total                       int64 on the device: the stream's length
+ *   d_member_offsets              int64 [members + 1] on the device, or NULL: where every member starts, then the total
+ * ATR_ERR_INVALID: a negative size, or out_capacity < atr_gzip_bound(n_bytes); ATR_ERR_UNSUPPORTED: n_bytes >= 4 GiB
+ * (the limit of the text tensors) -- both before any pointer is looked at. */
+#define ATR_GZIP_BLOCK 65280
+int64_t atr_gzip_bound(int64_t n_bytes);
+size_t atr_gzip_work_bytes(int64_t n_bytes);
+int atr_gzip_eof(uint8_t *buf28);                 /* fills the 28 bytes; returns 28 */
+int atr_gzip_blocks(const uint8_t *d_text, int64_t n_bytes, uint8_t *d_out, int64_t out_capacity, int64_t *d_total,
+                    int64_t *d_member_offsets, void *d_work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

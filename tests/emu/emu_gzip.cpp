@@ -1,0 +1,66 @@
+// TEST INFRASTRUCTURE: CPU twin of atropos_amd/csrc/gzip_kernels.hip (atr_gzip_bound, atr_gzip_work_bytes,
+// atr_gzip_blocks) built from the same per-block source (deflate_core.hpp) with -DATR_HOST_EMU: every phase of a
+// block is a loop over the kernel's lanes, in the kernel's phase and tile order, so that the compressor can be
+// developed and its corner cases checked without a GPU.  The compaction is two plain loops here.
+#include <stdint.h>
+#include <string.h>
+
+#include "atropos_hip.h"
+#include "deflate_core.hpp"
+
+using namespace atr;
+
+extern "C" {
+
+int64_t emu_gzip_bound(int64_t n_bytes) { return n_bytes < 0 ? (int64_t)ATR_ERR_INVALID : gz_bound(n_bytes); }
+
+size_t emu_gzip_work_bytes(int64_t n_bytes) { return n_bytes < 0 ? 0 : (size_t)gz_work_bytes(n_bytes); }
+
+int emu_gzip_eof(uint8_t *buf28) {
+    if (!buf28) return ATR_ERR_INVALID;
+    gz_eof_member(buf28);
+    return 28;
+}
+
+int emu_gzip_blocks(const uint8_t *text, int64_t n_bytes, uint8_t *out, int64_t out_capacity, int64_t *total,
+                    int64_t *member_offsets, void *work_buf) {
+    if (n_bytes < 0 || out_capacity < 0) return ATR_ERR_INVALID;
+    if (n_bytes >= ((int64_t)1 << 32)) return ATR_ERR_UNSUPPORTED;
+    if (out_capacity < gz_bound(n_bytes)) return ATR_ERR_INVALID;
+    if (!total) return ATR_ERR_INVALID;
+    if (n_bytes == 0) {
+        *total = 0;
+        if (member_offsets) member_offsets[0] = 0;
+        return ATR_OK;
+    }
+    if (!text || !out || !work_buf) return ATR_ERR_INVALID;
+    const int64_t nblocks = gz_nblocks(n_bytes);
+    uint8_t *work = (uint8_t *)work_buf;
+    uint32_t *sizes = (uint32_t *)(work + gz_work_sizes_at(n_bytes));
+    int64_t *offsets = (int64_t *)(work + gz_work_offsets_at(n_bytes));
+    static GzLds lds;                                      // (the emulation is single-threaded)
+    GzCtx c;
+    c.L = &lds;
+    c.m = (uint32_t *)(work + gz_work_match_at(n_bytes));
+    for (int64_t b = 0; b < nblocks; ++b) {
+        const int64_t at = b * GZ_BLOCK;
+        c.src = text + at;
+        c.n = (uint32_t)(n_bytes - at < GZ_BLOCK ? n_bytes - at : GZ_BLOCK);
+        c.slot = (uint32_t *)(work + (size_t)b * GZ_SLOT);
+        c.size = sizes + b;
+        gz_encode_block(c);
+    }
+    int64_t run = 0;
+    for (int64_t b = 0; b < nblocks; ++b) {
+        offsets[b] = run;
+        if (member_offsets) member_offsets[b] = run;
+        memcpy(out + run, work + (size_t)b * GZ_SLOT, sizes[b]);
+        run += sizes[b];
+    }
+    offsets[nblocks] = run;
+    if (member_offsets) member_offsets[nblocks] = run;
+    *total = run;
+    return ATR_OK;
+}
+
+}  // extern "C"
