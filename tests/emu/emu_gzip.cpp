@@ -63,4 +63,15 @@ int emu_gzip_blocks(const uint8_t *text, int64_t n_bytes, uint8_t *out, int64_t 
     return ATR_OK;
 }
 
+// gz_build_lengths driven directly (the code-length fuzz of test_gzip_host.py): freq[n] in ascending order, nonzero;
+// len_out[i] is the length of freq[i], blc_out[0 .. 15] the codes per length.
+int emu_gzip_build_lengths(const uint32_t *freq, int n, int maxbits, uint8_t *len_out, uint32_t *blc_out) {
+    if (!freq || !len_out || !blc_out || n < 0 || n > GZ_LL || maxbits < 1 || maxbits > 15) return ATR_ERR_INVALID;
+    uint32_t key[GZ_LL];
+    uint16_t sym[GZ_LL];
+    for (int i = 0; i < n; ++i) { key[i] = freq[i]; sym[i] = (uint16_t)i; len_out[i] = 0; }
+    gz_build_lengths(key, sym, n, maxbits, len_out, blc_out);
+    return ATR_OK;
+}
+
 }  // extern "C"

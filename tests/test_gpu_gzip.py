@@ -1,8 +1,11 @@
 """GPU tier of the device gzip compressor: the cases of tests/_gzip_common.py (the ones test_gzip_host.py runs on the
 CPU twin) through the gfx950 kernels -- ``HipBackend.gzip_blocks``, ``fastq.DeviceGzipSink`` and ``device_gzip=True``
-of the file drivers -- checked by ``gzip.decompress`` and ``zlib.decompress(member, 31)``."""
+of the file drivers -- checked by ``gzip.decompress``, ``zlib.decompress(member, 31)`` and, token by token, by the
+independent inflater and the plain model of tests/_deflate_ref.py; then the launch: more members than workgroups and
+than threads of the scan, members of unlike size, text at odd addresses."""
 import gzip
 
+import numpy as np
 import pytest
 import torch
 
@@ -16,13 +19,88 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("content", sorted(G.CONTENTS))
 def test_round_trip_and_structure(hip_backend, content):
-    for n in G.LENGTHS:
+    for n in G.case_lengths(content):
         data = G.CONTENTS[content](n)
         stream, starts = G.compress(hip_backend, data, offsets=True)
         members = G.check_stream(stream, data, starts, hip_backend.gzip_bound(n))
         if content == "random":
             for (at, size, isize) in members:
                 assert size <= isize + 31
+
+
+@pytest.mark.parametrize("content", sorted(G.CONTENTS))
+def test_tokens_and_codes(hip_backend, content):
+    """Every member of every case, read by the independent inflater: its tokens are those of the plain model of match
+    and parse -- a lost integer max, a table read before the tile before it was entered, a wrong cut at a segment's end
+    show here --, its codes are complete, monotone and optimal where no limit binds, its size is its bits."""
+    for n in G.case_lengths(content):
+        G.check_case(hip_backend, content, n)
+
+
+def test_fixture_conditions(hip_backend):
+    G.fixture_conditions(hip_backend)
+
+
+def _alone(backend, cache, block):
+    if block not in cache:
+        cache[block] = G.compress(backend, block)
+    return cache[block]
+
+
+@pytest.mark.parametrize("nblocks,tail", [(513, 5), (1025, 129)])
+def test_members_are_independent(hip_backend, nblocks, tail):
+    """A workgroup encodes blocks b, b + 512, ... with one LDS and one match array: after a full block rich in matches
+    come a stored block, a block without a match and a short one, and every member is, byte for byte, what its block
+    gives alone."""
+    rich = [G.CONTENTS[c](G.BLOCK) for c in ("one_byte", "every_symbol", "fibonacci")]
+    poor = [G.CONTENTS["random"](G.BLOCK), G.CONTENTS["no_match"](G.BLOCK), G._quiet()[:G.BLOCK]]
+    blocks = [rich[k % 3] if k < 512 else poor[k % 3] for k in range(nblocks - 1)] + [G._quiet()[:tail]]
+    stream, starts = G.compress(hip_backend, b"".join(blocks), offsets=True)
+    assert len(starts) == nblocks + 1 and starts[-1] == len(stream)
+    cache = {}
+    for k, block in enumerate(blocks):
+        assert stream[starts[k]:starts[k + 1]] == _alone(hip_backend, cache, block), "member %d" % k
+    for block, member in cache.items():
+        G.check_member(member, block, model=False)
+    assert sum(1 for b in blocks[512:] if len(_alone(hip_backend, cache, b)) == len(b) + 31) >= (nblocks - 513) // 3
+
+
+@pytest.mark.parametrize("nblocks", [1024, 1025, 2049])
+def test_scan_beyond_1024_members(hip_backend, nblocks):
+    """The scan gives a thread several members once there are more than 1024; the members differ in size."""
+    rnd = np.frombuffer(G.CONTENTS["random"](6000), dtype=np.uint8)
+    text = np.full((nblocks, G.BLOCK), ord("F"), dtype=np.uint8)
+    for k in range(7):
+        text[k::7, :k * 1000] = rnd[:k * 1000]
+    text[:, -1] = np.arange(nblocks) % 251                                 # (no two blocks alike)
+    data = text.tobytes()[:(nblocks - 1) * G.BLOCK + 777]
+    stream, starts = G.compress(hip_backend, data, offsets=True)
+    members = G.check_stream(stream, data, starts, hip_backend.gzip_bound(len(data)))
+    assert len(members) == nblocks and starts[-1] == len(stream)
+    assert len({size for _, size, _ in members}) >= 7
+
+
+def test_text_alignment(hip_backend):
+    """Text at 1, 2 and 3 bytes past an allocation, of lengths 4k + r for every r around one and two blocks (the last,
+    partial word of the byte-wise load), on two streams in turn: the bytes are those of the aligned text."""
+    base = G.CONTENTS["synth_fastq"](2 * G.BLOCK + 8)
+    lengths = [G.BLOCK + d for d in range(-3, 4)] + [2 * G.BLOCK + d for d in range(-3, 4)]
+    assert {n % 4 for n in lengths} == {0, 1, 2, 3}
+    dev = torch.frombuffer(bytearray(b"xyz" + base), dtype=torch.uint8).to(hip_backend.device)
+    streams = [torch.cuda.Stream(device=hip_backend.device) for _ in range(2)]
+    expect = {}
+    for i, (off, n) in enumerate((off, n) for off in (1, 2, 3) for n in lengths):
+        data = (b"xyz" + base)[off:off + n]
+        if data not in expect:
+            expect[data] = G.compress(hip_backend, data)                   # (from an allocation of its own: aligned)
+            G.check_stream(expect[data], data)
+        streams[i % 2].wait_stream(torch.cuda.current_stream(hip_backend.device))
+        with torch.cuda.stream(streams[i % 2]):
+            view = dev[off:off + n]
+            assert view.data_ptr() % 4 == (dev.data_ptr() + off) % 4 != 0
+            out, total = hip_backend.gzip_blocks(view)
+            got = bytes(out[:total].cpu().numpy().tobytes())
+        assert got == expect[data], (off, n)
 
 
 def test_deterministic_and_concatenation(hip_backend):
@@ -75,7 +153,11 @@ def test_ratio(hip_backend, kind):
 def test_same_bytes_as_the_twin(hip_backend):
     """The kernels and their CPU twin run one source (deflate_core.hpp): the streams are identical."""
     twin = G.GzipEmuBackend()
-    for data in (G.ratio_fixture("binned")[:3 * G.BLOCK + 99], G.CONTENTS["fibonacci"](G.BLOCK + 5), G.CONTENTS["random"](700)):
+    inputs = [G.ratio_fixture("binned")[:3 * G.BLOCK + 99], G.CONTENTS["fibonacci"](G.BLOCK + 5), G.CONTENTS["random"](700)]
+    for content, edge in (("cl_limit", 511), ("every_symbol", 16385), ("segment_cut", 4097), ("tail_match", 513),
+                          ("tail_match_far", 20480), ("window_edge", 32769 + 600)):
+        inputs += [G.CONTENTS[content](G.BLOCK), G.CONTENTS[content](edge)]
+    for data in inputs:
         assert G.compress(hip_backend, data) == G.compress(twin, data)
 
 

@@ -6,6 +6,7 @@ import gzip
 import os
 import subprocess
 
+import numpy as np
 import pytest
 import torch
 
@@ -27,19 +28,27 @@ def gz_backend(twin):
     _lib.set_backend(prev, _test_double=True)
 
 
-def test_fixture_conditions():
+def test_fixture_conditions(twin):
+    """What a fixture is named after is read from the parsed stream, not from how it was built.
+
+    ``dist_limit`` (a distance code that the 15-bit limit binds) is not among them.  It needs about 4 200 matches
+    whose distance symbols count like Fibonacci numbers, to within one match.  A generator that plants them one by
+    one where the one-entry hash table still holds the source, and feeds the model's counts back into its targets,
+    stayed at an unconstrained depth of 10 or 11 over 75 rounds: short runs and copies from near by match each other
+    by chance a hundred times a block.  That path of ``gz_build_lengths`` is covered by ``test_build_lengths_fuzz``."""
     assert G.huffman_depth(G.CONTENTS["fibonacci"](G.BLOCK)) > 15          # an unconstrained code would be too deep
     block = G.CONTENTS["no_match"](G.BLOCK)
     assert len({block[i:i + 3] for i in range(len(block) - 2)}) == len(block) - 2 and len(set(block)) == 256
-    tail = G.CONTENTS["tail_match"](G.BLOCK)
-    assert tail[-3:] == tail[:3]
+    quiet = G._quiet()
+    assert len({quiet[i:i + 3] for i in range(len(quiet) - 2)}) == len(quiet) - 2
+    G.fixture_conditions(twin)
     for kind in ("binned", "uniform"):
         assert (1 << 20) <= len(G.ratio_fixture(kind)) <= (5 << 18)
 
 
 @pytest.mark.parametrize("content", sorted(G.CONTENTS))
 def test_round_trip_and_structure(twin, content):
-    for n in G.LENGTHS:
+    for n in G.case_lengths(content):
         data = G.CONTENTS[content](n)
         assert len(data) == n
         stream, starts = G.compress(twin, data, offsets=True)
@@ -47,6 +56,57 @@ def test_round_trip_and_structure(twin, content):
         if content == "random":
             for (at, size, isize) in members:
                 assert size <= isize + 31
+
+
+@pytest.mark.parametrize("content", sorted(G.CONTENTS))
+def test_tokens_and_codes(twin, content):
+    """Every member of every case, read by the independent inflater: its tokens are those of the plain model of match
+    and parse, its three codes are complete, monotone and -- where no limit binds -- optimal, its size is its bits."""
+    worst = 0.0
+    for n in G.case_lengths(content):
+        for info in G.check_case(twin, content, n):
+            worst = max([worst] + info["ratios"])
+    if worst:
+        print("%s: a limited code costs at most %.4f of the package-merge optimum" % (content, worst))
+
+
+def _fuzz_histograms(rng, nmax, count):
+    fib = [1, 1]
+    while len(fib) < 40:
+        fib.append(fib[-1] + fib[-2])
+    for i in range(count):
+        n = int(rng.integers(2, nmax + 1))
+        kind = i % 6
+        if kind == 0:
+            f = fib[:min(n, 40)] + [fib[39]] * max(0, n - 40)
+        elif kind == 1:
+            f = [min(1 << min(k, 31), 0x7fffffff // nmax) for k in range(n)]
+        elif kind == 2:
+            f = [int(rng.integers(1, 100))] * n
+        elif kind == 3:
+            f = [1] * (n - 1) + [int(rng.integers(n, 1 << 20))]
+        elif kind == 4:
+            f = rng.integers(1, 1 << int(rng.integers(1, 20)), n).tolist()
+        else:
+            f = (rng.pareto(0.7, n) * 3 + 1).clip(1, 1 << 22).astype(int).tolist()
+        yield sorted(int(v) for v in f)
+
+
+@pytest.mark.parametrize("nmax,maxbits,count", [(19, 7, 3000), (286, 15, 1500)])
+def test_build_lengths_fuzz(twin, nmax, maxbits, count):
+    """``gz_build_lengths`` driven directly: the code properties over Fibonacci, geometric, all-equal, single-heavy,
+    uniform and heavy-tailed histograms; the limit binds in many of them."""
+    bound = worst = 0
+    for freqs in _fuzz_histograms(np.random.default_rng(nmax), nmax, count):
+        if sum(freqs) >= 1 << 32:
+            continue
+        lengths = G.twin_build_lengths(twin.gz, freqs, maxbits)
+        ratio = G.check_code(freqs, lengths, maxbits, "fuzz %r" % (freqs[:8],))
+        if ratio is not None:
+            bound += 1
+            worst = max(worst, ratio)
+    print("limit %d bound in %d histograms; worst cost / package-merge optimum %.4f" % (maxbits, bound, worst))
+    assert bound >= count // 20
 
 
 def test_deterministic_and_concatenation(twin):
