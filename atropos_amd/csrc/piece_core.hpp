@@ -43,6 +43,12 @@
 
 #include "filter_core.hpp"
 
+// pass A resolves clean read-end overlaps itself (piece_overlap_word); 0: every such read goes through pass B, as before
+// (the run-time compiled kernel: ATR_SPEC_FLAGS=-DATR_PIECE_OVERLAP_A=0)
+#ifndef ATR_PIECE_OVERLAP_A
+#define ATR_PIECE_OVERLAP_A 1
+#endif
+
 namespace atr {
 
 constexpr int PIECE_NB = 8;                 // body pieces at most: max(4, k + 1), k <= 6 (a piece too many only weakens the filter);
@@ -97,17 +103,59 @@ struct PieceParams {
     int aonly;                              // pass A ONLY (START_WITHIN_SEQ1 adapters of 33 .. 64 bases: pass B's one-word sweep cannot
                                             // take them -- no NARROW mode with column-0 starts): what pass A leaves goes to the window DP
                                             // with the columns pass A bounds, instead of the whole read as the one-pass pre-pass has it
+    uint32_t ovl_a;                         // bit i: pass A itself resolves a read whose longest perfect read-end overlap has i bases
+                                            // and whose every hit lies on that overlap's diagonal (piece_overlap_word); 0: never
 };
 
 // one-hot code (1, 2, 4, 8) -> plane index, -1 otherwise
 inline int piece_plane_of(int code) { return code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : -1; }
 
+// A CLEAN READ-END OVERLAP, DECIDED IN PASS A (ATR_PIECE_OVERLAP_A).  Almost half of C2's pass-B tasks are reads that end
+// in a perfect copy of the adapter's first i bases and hold nothing else of it: pass B sweeps 40 columns to find cell
+// (i, n) at cost 0 and then applies a certificate that depends on the adapter alone (filter_overlap_certificates).
+// Pass A's masks already hold all of that.  For an aligner without START_WITHIN_SEQ1, indel cost 1, at most 32 swept
+// rows: let i* be the LONGEST i <= 31 whose overlap is perfect (the read's last i bases match rows 0 .. i - 1 under the
+// aligner's comparison), d* = n - i* its diagonal.  If
+//   (a) min_overlap <= i* <= m - k - 1,
+//   (b) every hit of pass A -- body pieces (dm) and read-end pieces (tocc) -- lies on d*,
+//   (c) T* = max{t >= 0 : i* + t <= m, t <= thr_row[i* + t]} is 0, or T* <= FILTER_CERT_T with bit i* of cert[T*] set,
+// the reference returns (0, i*, n - i*, n, i*, 0):
+//   * No row-m candidate.  One of cost <= k keeps one of the >= k + 1 body pieces intact (they cover all m rows), pass A
+//     sees every exact occurrence of every piece that an alignment from row 0 can use, so the piece lies on d* and ends
+//     in a row e <= i*.  From (e, d* + e) to row m there are m - e rows and i* - e columns left: at least m - i* >= k + 1
+//     insertions.  (Ukkonen's cut-off leaves stale cells of cost > k >= thr_row[r] only: no candidates either.)
+//   * Cell (i*, n) costs 0, a pure diagonal: i* matches, origin d*, a candidate by (a).
+//   * A last-column row r < i* holds at most r < i* matches and loses (_align.pyx:464-474: more matches, then fewer errors).
+//   * A last-column row r > i* accepted with cost <= thr_row[r]: thr_row[r] = 0 would make the overlap of r bases perfect
+//     (r <= 31 contradicts the choice of i*, a longer one puts body piece 0 on diagonal n - r, against (b)); with
+//     thr_row[r] = t >= 1 the path keeps one of the class's t + 1 read-end pieces (or, for t >= PIECE_NT, body pieces)
+//     intact, inside tmask, hence on d* by (b), and ends on diagonal n - r: at least r - i* insertions.  So
+//     r - i* <= thr_row[r], i.e. r <= i* + T*, and the cost is exactly r - i* (down from (i*, n)).  T* = 0: no such
+//     row.  Otherwise row i* + T* is the largest acceptable row, its cost is T*, the rows between cost one more each:
+//     the very premise pass B verifies with (F.pvl & seg) == seg before it asks cert[T*] bit i*, which bounds the
+//     matches of ANY path of cost <= thr_row[i* + T*] to those rows by i* (a tie in matches loses to cost 0).
+// Wildcards (and_mode): cert is 0 there, so only T* = 0 remains, and that case never compares bases literally -- pieces,
+// insertions and match counts hold under the aligner's own comparison.  The word is 0 whenever a premise is off.
+// cert: FilterParams::cert (nullptr: no shortcut), indel: LocateParams::indel.
 #ifndef __HIPCC_RTC__
+inline uint32_t piece_overlap_word(const int32_t *thr_row, const uint32_t *cert, int m, int rows, int k, bool sr, int indel) {
+    if (!cert || sr || indel != 1 || rows > 32) return 0u;
+    uint32_t word = 0u;
+    for (int i = 1; i <= 31 && i <= m - k - 1; ++i) {
+        if (thr_row[i] < 0) continue;                                // below min_overlap / no STOP_WITHIN_SEQ1
+        int ts = 0;
+        for (int t = 1; i + t <= m; ++t) if (t <= thr_row[i + t]) ts = t;
+        if (ts == 0 || (ts <= FILTER_CERT_T && ((cert[ts] >> i) & 1u) != 0u)) word |= 1u << i;
+    }
+    return word;
+}
+
 // Host: does the two-pass pre-pass take this aligner (m rows, codes[], k, flags, thr_row as in FilterParams,
 // rows = FilterParams::rows) on equal-length reads of n bases?  Fills pp.
 // thr[L] = floor(L e) (LocateParams::thr), min_overlap: for the read-start classes of a START_WITHIN_SEQ1 aligner.
 inline bool piece_params(const uint8_t *codes, int m, int rows, int k, int flags, bool and_mode, bool custom_table,
-                         const int32_t *thr_row, int n, PieceParams &pp, const int16_t *thr = nullptr, int min_overlap = 1) {
+                         const int32_t *thr_row, int n, PieceParams &pp, const int16_t *thr = nullptr, int min_overlap = 1,
+                         const uint32_t *cert = nullptr, int indel = 0) {
     memset(&pp, 0, sizeof(pp));
     const int need = ATR_START_WITHIN_SEQ2 | ATR_STOP_WITHIN_SEQ2;
     if ((flags & need) != need || custom_table) return false;
@@ -263,6 +311,9 @@ inline bool piece_params(const uint8_t *codes, int m, int rows, int k, int flags
     pp.aonly = aonly ? 1 : 0;
     pp.steps = std::max(std::max(pp.llen, pp.tlen), pp.slen);
     pp.tail_cols = rows + k + (m - rows);                            // see "tail_cols" in DESIGN.md 3.2b: rows + k + T
+    // (a read-end piece of class t sits on a diagonal >= -t; aligned to piece 0's place the single-diagonal test keeps
+    //  the diagonals >= -(tlen - 1), as the body pieces' mask does with k <= blen - 1)
+    pp.ovl_a = (pp.tlen == 0 || tmax <= pp.tlen - 1) ? piece_overlap_word(thr_row, cert, m, rows, k, sr, indel) : 0u;
     return true;
 }
 #endif  // __HIPCC_RTC__ (host side)
@@ -510,7 +561,32 @@ struct PieceScan {
     bool tail;                               // a read-end condition holds (the window then ends at n)
     bool head;                               // START_WITHIN_SEQ1: a read-start condition holds (the window then starts at column 0;
                                              // the caller widens it: its columns are the read's own, j_s / j_e may be a moved read's)
+    int ovl;                                 // a clean read-end overlap of this many bases, resolved here (piece_overlap_word; 0: none):
+                                             // the record is (0, ovl, nr - ovl, nr, ovl, 0) in the read's own columns, flagged is false
 };
+
+// Condition (b) of piece_overlap_word for the read-end pieces: their hits moved to piece 0's place (piece u down by
+// u tlen <= 32 positions, as the body pieces' dm), bit b of the TWN tail words <=> a piece on diagonal b - (tlen - 1) of
+// that frame.  True when no bit but q is set (q outside the frame: no bit at all).
+template <int TWN>
+ATR_DEV bool piece_tail_on_diag(const uint32_t (&tocc)[PIECE_NT][TWN], int tlen, int q) {
+    const uint32_t bit = 1u << (q & 31);
+    const int qw = q >> 5;
+    uint32_t viol = 0u;
+#pragma unroll
+    for (int w = 0; w < TWN; ++w) {
+        uint32_t al = 0u;
+#pragma unroll
+        for (int u = 0; u < PIECE_NT; ++u) {
+            const int sh = u * tlen;                                 // 0 .. 32
+            const uint32_t lo = sh >= 32 ? (w + 1 < TWN ? tocc[u][w + 1 < TWN ? w + 1 : w] : 0u) : tocc[u][w];
+            const uint32_t hi = sh >= 32 ? (w + 2 < TWN ? tocc[u][w + 2 < TWN ? w + 2 : w] : 0u) : (w + 1 < TWN ? tocc[u][w + 1 < TWN ? w + 1 : w] : 0u);
+            al |= piece_funnel(hi, lo, sh & 31);
+        }
+        viol |= al & ~(qw == w ? bit : 0u);
+    }
+    return viol == 0u;
+}
 
 // What pass B (or the full sweep) is asked to do with a read, in the read's OWN columns.  back: positions pass A saw the read
 // moved up by (a ragged batch), nr: its length.  START_WITHIN_SEQ1: a read-start condition, or a body piece that allows a
@@ -587,21 +663,33 @@ ATR_DEV PieceScan piece_scan(const PieceParams &pp, const uint32_t (&pl)[NW][4],
             for (int w = 0; w < HWN; ++w) socc[u][w] = pp.smask[u][w];
     }
 
-    // (1) overlaps that must be exact: rows [0, i) against the last i bases, i in [xlo, xhi]: row r of an overlap
-    //     of i sits at bit 32 - i + r of the read's last 32 positions.
+    // (1) every perfect read-end overlap at once: row r of an overlap of i bases sits at bit 32 - i + r of the read's last
+    //     32 positions, so M = OR_r (neq[code of row r] >> r) has bit p CLEAR iff the overlap of 32 - p bases is perfect
+    //     (zeros shift in past the read end; positions before the read match nothing).  The overlaps that must be exact
+    //     (i in [xlo, xhi]) are a mask of it, the longest perfect one (piece_overlap_word) its lowest clear bit.
     bool tail = false;
-    if (xhi >= xlo) {
+    int istar = 0;
+    const uint32_t ovl_a = ATR_PIECE_OVERLAP_A ? (uint32_t)piece_uniform((int)pp.ovl_a) : 0u;
+    const int xrows = ovl_a != 0u ? atr_min(31, pm) : xhi >= xlo ? xhi : 0;      // rows 0 .. xrows - 1 (wave-uniform)
+    if (xrows > 0) {
         uint32_t tw[4];
         if (and_mode) { tw[0] = twp[0]; tw[1] = twp[1]; tw[2] = twp[2]; tw[3] = twp[3]; }
         else {
             tw[0] = twp[0] & ~(twp[1] | twp[2] | twp[3]); tw[1] = twp[1] & ~(twp[0] | twp[2] | twp[3]);
             tw[2] = twp[2] & ~(twp[0] | twp[1] | twp[3]); tw[3] = twp[3] & ~(twp[0] | twp[1] | twp[2]);
         }
-        for (int i = xlo; i <= xhi; ++i) {                     // wave-uniform trip count
-            // every row of the overlap matches <=> the four (mask & rows-of-that-code) words together fill bits 32 - i .. 31
-            const uint32_t mw = (tw[0] & pp.xmask[i][0]) | (tw[1] & pp.xmask[i][1]) | (tw[2] & pp.xmask[i][2]) | (tw[3] & pp.xmask[i][3]);
-            tail = tail || (i <= n && mw == (~0u << (32 - i)));
+        // (xmask[31][c]: the rows r < 31 that hold the code of plane c, at bit 1 + r)
+        const uint32_t r0 = (uint32_t)piece_uniform((int)pp.xmask[31][0]), r1 = (uint32_t)piece_uniform((int)pp.xmask[31][1]);
+        const uint32_t r2 = (uint32_t)piece_uniform((int)pp.xmask[31][2]), r3 = (uint32_t)piece_uniform((int)pp.xmask[31][3]);
+        uint32_t M = 0u;
+        for (int r = 0; r < xrows; ++r) {                          // wave-uniform trip count
+            const uint32_t eq = (tw[0] & (0u - ((r0 >> (r + 1)) & 1u))) | (tw[1] & (0u - ((r1 >> (r + 1)) & 1u))) |
+                                (tw[2] & (0u - ((r2 >> (r + 1)) & 1u))) | (tw[3] & (0u - ((r3 >> (r + 1)) & 1u)));
+            M |= ~eq >> r;
         }
+        const uint32_t nm = ~M & (~0u << (32 - atr_min(xrows, n)));  // overlaps of 1 .. xrows bases, inside the read
+        if (xhi >= xlo) tail = (nm & (xlo <= 1 ? ~0u : (1u << (33 - xlo)) - 1u) & (~0u << (32 - atr_min(xhi, n)))) != 0u;
+        if (ovl_a != 0u && nm != 0u) istar = 32 - atr_ctz(nm);
     }
 
     // (2) the pieces: body pieces on every word, read-end pieces on the read's last TWN words only
@@ -696,11 +784,22 @@ ATR_DEV PieceScan piece_scan(const PieceParams &pp, const uint32_t (&pl)[NW][4],
 #pragma unroll
     for (int w = NW - 1; w >= 0; --w) if (pf[w] != 0u) z_first = 32 * w + atr_ctz(pf[w]);
 
+    // a clean read-end overlap (piece_overlap_word): i* allowed by the host, every hit on its diagonal d* = n - i* -- in
+    // piece 0's place that is ONE bit, or none where the pieces are longer than the overlap
+    int ovl = 0;
+    if (ovl_a != 0u) {                                               // wave-uniform
+        const int qb = n - istar + pblen - 1;
+        const bool body_ok = b_first < 0 || (b_first == qb && b_last == qb);
+        const bool tail_ok = tlen == 0 || piece_tail_on_diag<TWN>(tocc, tlen, n - 32 * TW0 - istar + tlen - 1);
+        if (((ovl_a >> istar) & 1u) != 0u && body_ok && tail_ok && !head && z_first < 0) ovl = istar;
+    }
+
     const int tail_cols = piece_uniform(pp.tail_cols);
     PieceScan S;
     S.tail = tail;
     S.head = head;
-    S.flagged = tail || head || b_first >= 0;
+    S.ovl = ovl;
+    S.flagged = ovl == 0 && (tail || head || b_first >= 0);
     S.j_s = 0; S.j_e = 0;
     // the first zero-cost column of row m (all m rows verbatim on diagonal d: column d + m): where the reference stops
     S.j_exact = z_first >= 0 ? z_first - (pblen - 1) + pm : 0;
@@ -770,23 +869,29 @@ ATR_DEV PieceScan piece_scan_spec(const uint32_t (&pl)[NW][4], const uint32_t (&
             for (int w = 0; w < HWN; ++w) socc[u][w] = spec::PP.smask[u][w];
     }
 
-    // (1) overlaps that must be exact.  X_i = AND_{r < i} (tw[c_r] << (i - 1 - r)) has bit 31 set iff the last i bases
-    //     are rows 0 .. i - 1; X_{i + 1} = (X_i << 1) & tw[c_i]: one add and one and per overlap length.
+    // (1) every perfect read-end overlap at once (piece_scan): M |= neq[code of row r] >> r, a shift by a literal and an
+    //     or per row; the overlaps that must be exact are a literal mask of ~M, the longest perfect one its lowest bit.
     bool tail = false;
-    if constexpr (spec::PP.xhi >= spec::PP.xlo) {
-        uint32_t tw[4];
-        if constexpr (spec::PP.and_mode != 0) { tw[0] = twp[0]; tw[1] = twp[1]; tw[2] = twp[2]; tw[3] = twp[3]; }
+    int istar = 0;
+    constexpr uint32_t OVL = ATR_PIECE_OVERLAP_A ? spec::PP.ovl_a : 0u;
+    constexpr int XROWS = OVL != 0u ? (spec::PP.m < 31 ? spec::PP.m : 31) : spec::PP.xhi >= spec::PP.xlo ? spec::PP.xhi : 0;
+    if constexpr (XROWS > 0) {
+        uint32_t nq[4];
+        if constexpr (spec::PP.and_mode != 0) { nq[0] = ~twp[0]; nq[1] = ~twp[1]; nq[2] = ~twp[2]; nq[3] = ~twp[3]; }
         else {
-            tw[0] = twp[0] & ~(twp[1] | twp[2] | twp[3]); tw[1] = twp[1] & ~(twp[0] | twp[2] | twp[3]);
-            tw[2] = twp[2] & ~(twp[0] | twp[1] | twp[3]); tw[3] = twp[3] & ~(twp[0] | twp[1] | twp[2]);
+            nq[0] = ~twp[0] | (twp[1] | twp[2] | twp[3]); nq[1] = ~twp[1] | (twp[0] | twp[2] | twp[3]);
+            nq[2] = ~twp[2] | (twp[0] | twp[1] | twp[3]); nq[3] = ~twp[3] | (twp[0] | twp[1] | twp[2]);
         }
-        uint32_t x = ~0u, any = 0u;
-        piece_static_for<0, spec::PP.xhi>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;                   // row i joins: X_{i + 1}
-            x = (x + x) & tw[spec::ROWC[i]];
-            if constexpr (i + 1 >= spec::PP.xlo && i + 1 <= n) any |= x;
+        uint32_t M = 0u;
+        piece_static_for<0, XROWS>([&](auto ic) {
+            constexpr int r = decltype(ic)::value;
+            M |= nq[spec::ROWC[r]] >> r;
         });
-        tail = (any >> 31) != 0u;
+        constexpr int VR = XROWS < n ? XROWS : n, XH = spec::PP.xhi < n ? spec::PP.xhi : n;
+        const uint32_t nm = ~M & (~0u << (32 - VR));
+        if constexpr (spec::PP.xhi >= spec::PP.xlo)
+            tail = (nm & (spec::PP.xlo <= 1 ? ~0u : (1u << (33 - spec::PP.xlo)) - 1u) & (~0u << (32 - XH))) != 0u;
+        if constexpr (OVL != 0u) istar = nm != 0u ? 32 - atr_ctz(nm) : 0;
     }
 
     // (2) the pieces
@@ -886,10 +991,21 @@ ATR_DEV PieceScan piece_scan_spec(const uint32_t (&pl)[NW][4], const uint32_t (&
 #pragma unroll
     for (int w = NW - 1; w >= 0; --w) if (pf[w] != 0u) z_first = 32 * w + atr_ctz(pf[w]);
 
+    // a clean read-end overlap (piece_overlap_word, piece_scan)
+    int ovl = 0;
+    if constexpr (OVL != 0u) {
+        const int qb = n - istar + spec::PP.blen - 1;
+        const bool body_ok = b_first < 0 || (b_first == qb && b_last == qb);
+        bool tail_ok = true;
+        if constexpr (spec::PP.tlen > 0) tail_ok = piece_tail_on_diag<TWN>(tocc, spec::PP.tlen, n - 32 * TW0 - istar + spec::PP.tlen - 1);
+        if (((OVL >> istar) & 1u) != 0u && body_ok && tail_ok && !head && z_first < 0) ovl = istar;
+    }
+
     PieceScan S;
     S.tail = tail;
     S.head = head;
-    S.flagged = tail || head || b_first >= 0;
+    S.ovl = ovl;
+    S.flagged = ovl == 0 && (tail || head || b_first >= 0);
     S.j_s = 0; S.j_e = 0;
     S.j_exact = z_first >= 0 ? z_first - (spec::PP.blen - 1) + spec::PP.m : 0;
     if (b_first >= 0) {

@@ -422,10 +422,14 @@ __device__ __forceinline__ void piece_filter_body(const LocateParams &p, const F
             const int j = S.j_exact - back;                       // in the read's own columns
             out[r] = make_uint4((uint32_t)u.m << 16, (uint32_t)(j - u.m) | ((uint32_t)j << 16), (uint32_t)u.m, 0u);
         }
+        // a clean read-end overlap: resolved here as well (piece_overlap_word), no pass B (13.1 % of C2's reads, counted by the
+        // CPU twin of pass A on 200 000 reads of the synthetic workload -- not a device counter)
+        const bool ovl = ATR_PIECE_OVERLAP_A != 0 && live && S.ovl != 0 && !exact;
+        if (ovl) out[r] = make_uint4((uint32_t)S.ovl << 16, (uint32_t)(nr - S.ovl) | ((uint32_t)nr << 16), (uint32_t)S.ovl, 0u);
         const bool flagged = live && pt.flagged && !exact;
         if (piece_uniform(pp.aonly) != 0) {                       // (wave-uniform; a constant of the run-time compiled kernel)
             // pass A only: None / the adapter verbatim decided above, every other read to the window DP with pass A's columns
-            if (live && !flagged && !exact) out[r] = make_uint4(0xFFFF0000u, 0u, 0u, 0u);
+            if (live && !flagged && !exact && !ovl) out[r] = make_uint4(0xFFFF0000u, 0u, 0u, 0u);
             const int wlo = pt.full ? 0 : pt.j_e - pt.need, whi = pt.full ? nr : pt.j_e;
             const uint32_t ww = flagged ? window_word(wlo, whi, whi == nr, u.m, false) : 0u;
             const uint32_t none[4] = {0xFFFF0000u, 0u, 0u, 0u};
@@ -434,7 +438,7 @@ __device__ __forceinline__ void piece_filter_body(const LocateParams &p, const F
         }
         const int need = pt.need;                                 // (columns before the read: nothing to sweep)
         const bool narrow = flagged && !pt.full && need <= piece_uniform(pp.narrow), wide = flagged && !narrow;
-        if (live && !flagged && !exact) out[r] = make_uint4(0xFFFF0000u, 0u, 0u, 0u);   // None
+        if (live && !flagged && !exact && !ovl) out[r] = make_uint4(0xFFFF0000u, 0u, 0u, 0u);   // None
         // (the task carries the read's own columns: a ragged batch was scanned moved to the end of its words)
         const uint32_t meta = (uint32_t)pt.j_e | ((uint32_t)need << 10) | (RAGGED ? (uint32_t)nr << 17 : 0u);
         {

@@ -21,7 +21,7 @@ int main(int argc, char **argv) {
     const int nw = (max_len + 31) / 32, n = ragged ? 32 * nw : max_len;
     const FilterParams fp = filter_params(a->peq, a->codes, a->p.m, a->flags, false, a->p.thr, a->p.min_overlap, true);
     PieceParams pp;
-    if (!piece_params(a->codes, a->p.m, fp.rows, a->p.k, a->flags, false, a->table_kind == ATR_TABLE_CUSTOM, fp.thr_row, n, pp, a->p.thr, a->p.min_overlap)) {
+    if (!piece_params(a->codes, a->p.m, fp.rows, a->p.k, a->flags, false, a->table_kind == ATR_TABLE_CUSTOM, fp.thr_row, n, pp, a->p.thr, a->p.min_overlap, fp.cert, a->p.indel)) {
         fprintf(stderr, "outside the two-pass envelope\n");
         return 1;
     }
@@ -31,7 +31,7 @@ int main(int argc, char **argv) {
     if (!f) { perror("open"); return 1; }
     fwrite(cfg.data(), 1, cfg.size(), f);
     fclose(f);
-    printf("NW=%d RAGGED=%d n=%d blen=%d llen=%d tlen=%d steps=%d xlo=%d xhi=%d\n", nw, (int)ragged, n, pp.blen, pp.llen, pp.tlen, pp.steps, pp.xlo, pp.xhi);
+    printf("NW=%d RAGGED=%d n=%d blen=%d llen=%d tlen=%d steps=%d xlo=%d xhi=%d ovl_a=0x%x\n", nw, (int)ragged, n, pp.blen, pp.llen, pp.tlen, pp.steps, pp.xlo, pp.xhi, pp.ovl_a);
     if (argc > 8 && !strcmp(argv[8], "--rtc")) {
         std::string log;
         const std::vector<char> code = jit::compile_spec(cfg, nw, ragged, 0, "gfx950", &log);
