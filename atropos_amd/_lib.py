@@ -212,8 +212,11 @@ PROTOTYPES = {
     "atr_gzip_work_bytes": (C.c_size_t, [C.c_int64]),
     "atr_gzip_eof": (C.c_int, [C.c_void_p]),
     "atr_gzip_blocks": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+    "atr_bgzf_scan": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4),
+    "atr_gunzip_members": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
 }
 GZIP_BLOCK = 65280                       # atr_gzip_blocks: bytes of text per BGZF member
+GUNZIP_MAX_MEMBERS = 1 << 22             # atr_gunzip_members: members of one call (ATR_GUNZIP_MAX_MEMBERS)
 GZIP_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")  # atr_gzip_eof
 DETECT_MAX_READ = 320                    # atr_detect_*: reads up to here (the complexity table is (len + 1)^2 doubles)
 DETECT_HDR = 8                           # detect_core.hpp: kept, distinct, invalid, overlong, then 4 x nseq counters
@@ -270,6 +273,22 @@ def _check(lib, rc, what):
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _bgzf_scan(fn, buf, lo, hi, max_members):
+    # (the arguments are checked here, so that the function's ATR_ERR_INVALID can only mean "not a BGZF header")
+    lo, hi, max_members = int(lo), int(hi), int(max_members)
+    if (not isinstance(buf, torch.Tensor) or buf.device.type != "cpu" or buf.dtype != torch.uint8 or not buf.is_contiguous()
+            or not 0 <= lo <= hi <= buf.numel() or max_members < 0):
+        raise ValueError("bgzf_scan: a contiguous uint8 host tensor, 0 <= lo <= hi <= its size and max_members >= 0 are needed")
+    member_at = torch.zeros((int(max_members) + 1,), dtype=torch.int64)
+    text_at = torch.zeros((int(max_members) + 1,), dtype=torch.int64)
+    k, covered = C.c_int64(0), C.c_int64(0)
+    rc = fn(C.c_void_p(buf.data_ptr() + int(lo)), C.c_int64(int(hi) - int(lo)), C.c_int64(int(max_members)), _ptr(member_at),
+            _ptr(text_at), C.byref(k), C.byref(covered))
+    if rc not in (0, -1):
+        raise AtroposHipError("atr_bgzf_scan: error %d" % rc)
+    return member_at, text_at, int(k.value), int(covered.value), rc == 0
 
 
 class _PinnedUpload(object):
@@ -1017,6 +1036,26 @@ class HipBackend(object):
                                                       self._stream()), "atr_gzip_blocks")
             size = int(total.item())
         return (out, size, starts) if offsets else (out, size)
+
+    # -- BGZF .gz input on the device (atr_bgzf_scan, atr_gunzip_members) ------------------------------------------
+    def bgzf_scan(self, buf, lo, hi, max_members):
+        """The whole BGZF members at the front of ``buf[lo:hi]`` (a uint8 HOST tensor), at most ``max_members``:
+        (member_at, text_at, k, covered, ok) -- int64 host tensors whose entries 0 .. k are the members' offsets from
+        ``lo`` and the running sum of their text sizes; ``covered`` = member_at[k]; ``ok`` is False when the walk
+        stopped at a header that is no BGZF member (at ``lo + covered``)."""
+        return _bgzf_scan(self.lib.atr_bgzf_scan, buf, lo, hi, max_members)
+
+    def gunzip_members(self, stream, n_stream, member_at, text_at, n_members, text, capacity):
+        """Inflate ``n_members`` BGZF members of ``stream`` (uint8 device tensor, readable to the next multiple of 16
+        beyond ``n_stream``) into ``text[text_at[m]:text_at[m + 1]]``; ``member_at`` / ``text_at``: int64 device
+        tensors.  Returns (status int32 [n_members], bad int32 [1]) on the device: nothing here waits for the kernel."""
+        status = self.empty((max(int(n_members), 1),), torch.int32)
+        bad = self.empty((1,), torch.int32)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.atr_gunzip_members(_ptr(stream), int(n_stream), _ptr(member_at), _ptr(text_at), int(n_members),
+                                                         _ptr(text), int(capacity), _ptr(status), _ptr(bad), self._stream()),
+                   "atr_gunzip_members")
+        return status, bad
 
     # -- read statistics (atr_read_stats_*) ---------------------------------------------------------------------
     def read_stats_words(self, max_len):

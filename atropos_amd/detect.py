@@ -462,11 +462,12 @@ class PairedDetector(object):
 def _detect_paths(paths, detector_class, known_contaminants, max_reads, chunk_bytes, kwargs):
     """The chunks of ``fastq.read_chunks`` into a detector until ``max_reads`` records went in; its summary."""
     report = {k: kwargs.pop(k) for k in ("min_len", "min_complexity", "min_match_frac", "limit") if k in kwargs}
+    device_gunzip = kwargs.pop("device_gunzip", False)        # (BGZF .gz input inflated on the GPU: fastq.ChunkedFastqReader)
     kwargs.setdefault("n_reads", max_reads)
     det = detector_class(known_contaminants, **kwargs)
     try:
         left = max_reads
-        for batches in read_chunks(paths, chunk_bytes):
+        for batches in read_chunks(paths, chunk_bytes, device_gunzip=device_gunzip):
             if left is not None:
                 batches = [b.head(left)[0] for b in batches]
                 left -= len(batches[0])
@@ -481,7 +482,8 @@ def _detect_paths(paths, detector_class, known_contaminants, max_reads, chunk_by
 def detect_file(path, known_contaminants, max_reads=10000, chunk_bytes=64 << 20, **kwargs):
     """``atropos detect --detector known`` of one FASTQ file, read in chunks, stopping after ``max_reads`` records
     (None: the whole file, which must fit one batch -- see the module doc).  ``n_reads`` defaults to ``max_reads``.
-    Returns the reference's ``summary['detect']`` dict; ``matches`` is a 1-tuple of lists."""
+    Returns the reference's ``summary['detect']`` dict; ``matches`` is a 1-tuple of lists.  ``device_gunzip=True``
+    (here and in ``detect_files``): BGZF ``.gz`` input is inflated on the GPU."""
     return _detect_paths([path], KnownContaminantDetector, known_contaminants, max_reads, chunk_bytes, kwargs)
 
 

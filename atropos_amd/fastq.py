@@ -11,6 +11,7 @@ import collections
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import ExitStack
 
 import torch
 
@@ -348,6 +349,15 @@ class ChunkedFastqReader(object):
     ``.gz`` / ``.bz2`` / ``.xz`` input (what the reference's xopen opens by extension) is decompressed by one
     read-ahead thread straight into the staging buffer: the decompressor then sets the pace.
 
+    ``device_gunzip=True`` and a ``.gz`` file whose first member is BGZF (what ``bgzip``, htslib and ``device_gzip=True``
+    write: members of at most 64 KiB that carry their own size): the COMPRESSED bytes take the plain-file road -- slabs
+    read ahead with the ``pread`` pool and walked member by member on the host (``bgzf_scan``), a job that never waits
+    for the GPU -- and are inflated on the device (``gunzip_members``, a wave per member) straight into the chunk's text
+    tensor behind the carried-over tail, which is a device-to-device copy: the text never visits the host.
+    ``inflate_path`` says which road a reader took: "device", "host" (any other ``.gz``: unchanged), or None.  The flag
+    wants BGZF throughout: a later member that is not BGZF, or one that fails its checks, is a ``gzip.BadGzipFile``
+    naming the member's file offset; a file that ends inside a member is an ``EOFError``.
+
     ``byte_range`` = (lo, hi): only these bytes of a plain file, which must be whole records (a rank's shard,
     ``shard.fastq_shard_ranges``).  The loop that drives a reader -- ``next_batch``, ``advance``, ``close``, and two
     readers in lock step -- is ``read_chunks``; nothing else constructs one."""
@@ -355,7 +365,9 @@ class ChunkedFastqReader(object):
     READ_AHEAD = 3
     RESERVE = 64 << 20                                       # room for the carried-over tail of the previous chunk
 
-    def __init__(self, path, chunk_bytes, backend=None, clock=None, byte_range=None):
+    BGZF_SCAN = 4096                                         # members per bgzf_scan call
+
+    def __init__(self, path, chunk_bytes, backend=None, clock=None, byte_range=None, device_gunzip=False):
         name = str(path)
         if byte_range is not None and name.endswith((".gz", ".bz2", ".xz")):
             raise ValueError("a byte range of compressed input: the offsets are those of the plain text")
@@ -368,7 +380,11 @@ class ChunkedFastqReader(object):
         self.fd = self.file.fileno()
         self.pos, self.size = byte_range or (0, os.path.getsize(path))      # (plain files: the next pread, the end)
         self.stream = None
-        if name.endswith(".gz"):
+        self.inflate_path = "host" if name.endswith(".gz") else None
+        self.bgzf = bool(device_gunzip and name.endswith(".gz") and self._starts_with_bgzf())
+        if self.bgzf:
+            self.inflate_path = "device"
+        elif name.endswith(".gz"):
             import gzip
             self.stream = gzip.open(self.file, "rb")
         elif name.endswith(".bz2"):
@@ -388,6 +404,20 @@ class ChunkedFastqReader(object):
         self.final = False
         if self.stream is not None:
             self.pending = self.ahead.submit(self._fill, 0, b"")
+        elif self.bgzf:
+            self.reads = collections.deque()                 # futures of _read_slab
+            self.next_slot = 0
+            self.carry_est = 0
+            self.ratio = 1.0                                 # compressed bytes per byte of text, as last seen
+            self.uploaded = [None] * len(self.buf)
+            self.data = None
+            try:
+                for _ in range(self.READ_AHEAD):
+                    self.reads.append(self.ahead.submit(self._read_slab))
+                self.pending = self._assemble_device(None)
+            except BaseException:
+                self.close()                                  # (nobody else holds the file and the two thread pools yet)
+                raise
         else:
             self.reads = collections.deque()                 # (slot, pread jobs, bytes asked for, last chunk of the file)
             self.next_slot = 0
@@ -465,6 +495,119 @@ class ChunkedFastqReader(object):
         self._issue_read()                                    # the buffer of the chunk before this one is free again
         return nbytes, final, unterminated, data, ready, host
 
+    # ---- BGZF input: compressed slabs read and scanned ahead, inflated on the device
+    def _starts_with_bgzf(self):
+        head = torch.frombuffer(bytearray(os.pread(self.fd, 65536, 0)), dtype=torch.uint8) if self.size else None
+        return head is not None and self.be.bgzf_scan(head, 0, head.numel(), 1)[4]
+
+    def _read_slab(self):
+        """(read-ahead thread) The next slab of compressed bytes and its whole members, as many as hold the text of
+        a chunk.  Nothing here waits for the GPU but the reuse of a staging buffer three chunks later."""
+        slot = self.next_slot
+        self.next_slot = (slot + 1) % len(self.buf)
+        if self.uploaded[slot] is not None:
+            self.uploaded[slot].synchronize()
+            self.uploaded[slot] = None
+        budget = max(self.chunk_bytes - self.carry_est, self.chunk_bytes // 4)
+        room = self.buf[slot].numel() - 32
+        want = min(self.size - self.pos, room, max(int(budget * self.ratio * 1.25) + (128 << 10), 1 << 17))
+        view = memoryview(self.buf[slot].numpy())
+        step = ((want + IO_THREADS - 1) // IO_THREADS + 4095) & ~4095
+        jobs = []
+        for t in range(IO_THREADS):
+            lo, hi = t * step, min(want, (t + 1) * step)
+            if hi > lo:
+                jobs.append(self.readers.submit(os.preadv, self.fd, [view[lo:hi]], self.pos + lo))
+        if sum(j.result() for j in jobs) != want:
+            raise IOError("short read: the input file changed while it was being read")
+        at_end = self.pos + want >= self.size
+        member_at, text_at, k, covered, error = [0], [0], 0, 0, None
+        while covered < want and text_at[-1] <= budget and k + self.BGZF_SCAN <= _lib.GUNZIP_MAX_MEMBERS:
+            m_at, t_at, n, took, ok = self.be.bgzf_scan(self.buf[slot], covered, want, self.BGZF_SCAN)
+            member_at += [covered + v for v in m_at[1:n + 1].tolist()]
+            text_at += [text_at[-1] + v for v in t_at[1:n + 1].tolist()]
+            k += n
+            covered += took
+            if not ok:
+                import gzip
+                error = gzip.BadGzipFile("not a BGZF member at file offset %d (device_gunzip wants BGZF throughout)" % (self.pos + covered))
+            if not ok or n < self.BGZF_SCAN:
+                break
+        while k > 1 and text_at[k] > budget:                  # (members are taken while their text fits)
+            k -= 1
+        if k:
+            error = None                                      # (the member behind these opens the next slab)
+        elif error is None and at_end and want:
+            error = EOFError("Compressed file ended before the end-of-stream marker was reached")
+        elif error is None and want:
+            raise IOError("no whole BGZF member in %d bytes at file offset %d" % (want, self.pos))
+        covered = member_at[k]
+        if text_at[k]:
+            self.ratio = covered / float(text_at[k])
+        pos = self.pos
+        self.pos += covered
+        return slot, pos, covered, member_at[:k + 1], text_at[:k + 1], self.pos >= self.size, error
+
+    def _assemble_device(self, carry):
+        """The next chunk: [carried-over text | the text of the next slab's members], both put there on the device."""
+        t0 = time.perf_counter()
+        slot, pos, n, member_at, text_at, final, error = self.reads.popleft().result()
+        self.clock.add("wait_file_read", t0)
+        if error is not None:
+            return error                                      # (raised when this chunk is asked for)
+        k, total = len(member_at) - 1, text_at[-1]
+        n0 = carry[2] - carry[1] if carry else 0
+        nbytes = n0 + total
+        host = self.buf[slot]
+        up = self.upload_stream
+        status = bad = ready = None
+        with ExitStack() as on_upload_stream:
+            if up is not None:
+                on_upload_stream.enter_context(torch.cuda.device(self.be.device))
+                on_upload_stream.enter_context(torch.cuda.stream(up))
+            data = self.be.empty(((nbytes + 15) // 16 * 16 + 16,), torch.uint8)
+            if n0:
+                data[:n0].copy_(carry[0][carry[1]:carry[2]])
+            if k:
+                comp = self.be.empty(((n + 15) // 16 * 16,), torch.uint8)
+                comp[:n].copy_(host[:n], non_blocking=True)
+                comp[n:].zero_()
+                offsets = torch.tensor([member_at, text_at], dtype=torch.int64).to(self.be.device)
+                status, bad = self.be.gunzip_members(comp, n, offsets[0], offsets[1], k, data[n0:], total)
+            data[nbytes:].zero_()
+            if up is not None:
+                ready = torch.cuda.Event()
+                ready.record()
+        self.uploaded[slot] = ready
+        self.reads.append(self.ahead.submit(self._read_slab))  # (past the end of the file: an empty, final slab)
+        return nbytes, final, data, ready, status, bad, pos, member_at
+
+    def _next_device(self):
+        res = self.pending
+        if isinstance(res, BaseException):
+            raise res
+        nbytes, self.final, data, ready, status, bad, pos, member_at = res
+        if ready is not None:
+            with torch.cuda.device(self.be.device):
+                cur = torch.cuda.current_stream()
+                cur.wait_event(ready)
+                for t in (data, status, bad):
+                    if t is not None:
+                        t.record_stream(cur)
+        if bad is not None and int(bad.item()):
+            import gzip
+            first = int(torch.nonzero(status)[0].item())
+            raise gzip.BadGzipFile("BGZF member at file offset %d fails its checks (status %d of inflate_core.hpp)"
+                                   % (pos + member_at[first], int(status[first].item())))
+        unterminated = bool(self.final and nbytes and int(data[nbytes - 1].item()) not in (10, 13))
+        if unterminated:
+            data[nbytes] = 10                                 # tolerate a missing last newline (_seqio.pyx:240-243)
+            nbytes += 1
+            if ready is not None:                             # (the carry is copied on the upload stream)
+                self.upload_stream.wait_stream(torch.cuda.current_stream(self.be.device))
+        self.data, self.nbytes = data, nbytes
+        return data, nbytes, unterminated
+
     # ---- compressed input: one sequential decompressor, one chunk ahead
     def _fill(self, k, carry):
         view = memoryview(self.buf[k].numpy())
@@ -500,6 +643,11 @@ class ChunkedFastqReader(object):
     def next_batch(self):
         """Upload and index the next chunk; returns the FastqBatch of its whole records."""
         t0 = time.perf_counter()
+        if self.bgzf:
+            data, nbytes, unterminated = self._next_device()
+            batch, self.consumed = FastqBatch.from_device(data, nbytes, self.final, self.be, unterminated=unterminated)
+            self.clock.add("upload_and_index", t0)
+            return batch
         res = self.pending.result() if hasattr(self.pending, "result") else self.pending
         self.nbytes, self.final, unterminated, data, ready, self.host = res
         if self.stream is not None:
@@ -525,6 +673,13 @@ class ChunkedFastqReader(object):
         buffer already, its upload starts here).  Returns True when the file is exhausted and nothing is
         carried over."""
         consumed = self.consumed if consumed is None else consumed
+        if self.bgzf:
+            n0 = self.nbytes - consumed
+            if self.final and not n0:
+                return True
+            self.carry_est = n0
+            self.pending = self._assemble_device((self.data, consumed, self.nbytes) if n0 else None)
+            return False
         carry = bytes(self.host[consumed:self.nbytes].numpy().tobytes())
         if self.final and not carry:
             return True
@@ -536,7 +691,13 @@ class ChunkedFastqReader(object):
         return False
 
     def close(self):
-        if self.stream is None:
+        if self.bgzf:
+            for fut in self.reads:
+                fut.exception()                               # (a slab still being read owns its buffer)
+            for ev in self.uploaded:
+                if ev is not None:
+                    ev.synchronize()
+        elif self.stream is None:
             for _, jobs, _, _ in self.reads:                  # reads still in flight own their buffers
                 for j in jobs:
                     j.result()
@@ -550,7 +711,7 @@ class ChunkedFastqReader(object):
         self.buf = []
 
 
-def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None):
+def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, device_gunzip=False):
     """THE chunk loop of every file driver (trim, qc, error rate, detect, a rank's shard): yields a list of
     FastqBatch, one per path, chunk after chunk of whole records.  Several paths are read in lock step: every
     batch of a list holds the same number of records (the file whose chunk holds fewer decides, the surplus of the
@@ -559,12 +720,13 @@ def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None):
     The next chunk is put together, and its upload started, BEFORE a chunk is handed out: that copy runs while the
     consumer works.  A chunk may hold no whole record; it is yielded all the same.  The readers are closed when the
     loop ends, however it ends -- a consumer that has enough just leaves its ``for`` loop.  ``byte_ranges``: one
-    (lo, hi) or None per path (``ChunkedFastqReader``)."""
+    (lo, hi) or None per path (``ChunkedFastqReader``).  ``device_gunzip``: BGZF ``.gz`` input is inflated on the GPU
+    (``ChunkedFastqReader``); every other input is read as without it."""
     mismatch = "the two input files hold different numbers of records"
     readers = []
     try:
         for path, byte_range in zip(paths, byte_ranges or [None] * len(paths)):
-            readers.append(ChunkedFastqReader(path, chunk_bytes, backend, clock, byte_range))
+            readers.append(ChunkedFastqReader(path, chunk_bytes, backend, clock, byte_range, device_gunzip))
         while True:
             batches = [r.next_batch() for r in readers]
             if len(readers) == 1:

@@ -304,28 +304,29 @@ class PairedEndReadStatistics(object):
 
 # ---------------------------------------------------------------------------------------------- file drivers
 # (every chunk of ``fastq.read_chunks`` into the counters: one file, or two in lock step)
-def qc_file(path, chunk_bytes=64 << 20, quality_base=33, qualities=True):
-    """``atropos qc`` of one FASTQ file: {"pre": {0: {"read1": summary}}} (QcPipeline.finish)."""
+def qc_file(path, chunk_bytes=64 << 20, quality_base=33, qualities=True, device_gunzip=False):
+    """``atropos qc`` of one FASTQ file: {"pre": {0: {"read1": summary}}} (QcPipeline.finish).  ``device_gunzip``
+    (here and in the drivers below): BGZF ``.gz`` input is inflated on the GPU (``fastq.ChunkedFastqReader``)."""
     st = SingleEndReadStatistics(qualities=qualities, quality_base=quality_base)
-    for batches in read_chunks([path], chunk_bytes):
+    for batches in read_chunks([path], chunk_bytes, device_gunzip=device_gunzip):
         st.collect_batch(*batches)
     return {"pre": {0: st.summarize()}}
 
 
-def qc_files(path1, path2, chunk_bytes=64 << 20, quality_base=33, qualities=True):
+def qc_files(path1, path2, chunk_bytes=64 << 20, quality_base=33, qualities=True, device_gunzip=False):
     """``atropos qc`` of paired files: {"pre": {0: {"read1": ..., "read2": ...}}}."""
     st = PairedEndReadStatistics(qualities=qualities, quality_base=quality_base)
-    for batches in read_chunks([path1, path2], chunk_bytes):
+    for batches in read_chunks([path1, path2], chunk_bytes, device_gunzip=device_gunzip):
         st.collect_batch(*batches)
     return {"pre": {0: st.summarize()}}
 
 
-def error_rate_file(path, path2=None, max_bases=None, chunk_bytes=64 << 20):
+def error_rate_file(path, path2=None, max_bases=None, chunk_bytes=64 << 20, device_gunzip=False):
     """``atropos error -a quality``: (estimates, total_lens), one entry per input file, as
     BaseQualityErrorEstimator / PairedErrorEstimator put them in the summary."""
     paths = [path] if path2 is None else [path, path2]
     sts = [ReadStatistics(qualities=True) for _ in paths]
-    for batches in read_chunks(paths, chunk_bytes):
+    for batches in read_chunks(paths, chunk_bytes, device_gunzip=device_gunzip):
         for st, batch in zip(sts, batches):
             st.collect_batch(batch)
     res = [s.error_rate(max_bases) for s in sts]

@@ -289,7 +289,7 @@ def _run_stages(pipes, mates, insert_stage=None):
 
 
 def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out=None, byte_ranges=None,
-                 device_gzip=False):
+                 device_gzip=False, device_gunzip=False):
     """What ``TrimPipeline.trim_file`` (one input), ``PairedTrimPipeline.trim_files`` (two inputs in lock step) and
     ``shard.sharded_trim_file`` (``byte_ranges``: a rank's part of the input) do with every chunk of
     ``fastq.read_chunks``; returns the destination counts."""
@@ -304,13 +304,13 @@ def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
                 raise ValueError("device_gzip: the output path must end in .gz (%r)" % str(p))
     if not pipe.report:
         return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, None,
-                            device_gzip)
+                            device_gzip, device_gunzip)
     # the report's counters: made before any output is opened (the table bound refuses here), on the device until the
     # file is done
     report = TrimReport(pipe, source=tuple(paths_in) if len(paths_in) == 2 else paths_in[0])
     try:
         return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report,
-                            device_gzip)
+                            device_gzip, device_gunzip)
     finally:
         report.close()
 
@@ -321,9 +321,10 @@ def pipe_demultiplexes(pipe, paths_out, merged_out=None):
 
 
 def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report,
-                 device_gzip=False):
+                 device_gzip=False, device_gunzip=False):
     """The chunk loop of ``_trim_stream``; ``report``: the run's TrimReport or None; ``device_gzip``: the main
-    outputs and the merged output through ``fastq.DeviceGzipSink`` (side files stay on the host path)."""
+    outputs and the merged output through ``fastq.DeviceGzipSink`` (side files stay on the host path);
+    ``device_gunzip``: BGZF ``.gz`` input inflated on the GPU (``fastq.ChunkedFastqReader``)."""
     paired = len(paths_in) == 2
     first = pipe.p1 if paired else pipe
     merging = paired and pipe.merge_overlapping
@@ -354,7 +355,7 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
                                    device_gzip=device_gzip))
     stats = TrimStats(pipe.stats, paired, first.quality_base) if pipe.stats else None
     try:
-        for batches in read_chunks(paths_in, chunk_bytes, be, clock, byte_ranges):
+        for batches in read_chunks(paths_in, chunk_bytes, be, clock, byte_ranges, device_gunzip):
             t0 = time.perf_counter()
             if stats is not None and stats.pre is not None:
                 stats.pre.collect_batch(*batches)             # before any stage writes into the chunks
@@ -803,7 +804,8 @@ class TrimPipeline(object):
         batch, _ = FastqBatch.from_bytes(data, final=True)
         return self.run(batch).text(which)
 
-    def trim_file(self, path_in, path_out, chunk_bytes=256 << 20, keep_output=False, output_parts=1, device_gzip=False):
+    def trim_file(self, path_in, path_out, chunk_bytes=256 << 20, keep_output=False, output_parts=1, device_gzip=False,
+                  device_gunzip=False):
         """Stream a FASTQ file through the GPU in chunks of whole records; returns the
         destination counts.  (Plain files; compressed input is the caller's business.)
         Host side: ``fastq.read_chunks`` (the one chunk loop, over ``ChunkedFastqReader``) / ``FastqSink`` (page-locked staging buffers, threaded
@@ -823,11 +825,17 @@ class TrimPipeline(object):
 
         ``device_gzip``: ``path_out`` ends in ``.gz`` and is compressed on the GPU (``fastq.DeviceGzipSink``: BGZF
         members, any gzip reader takes them) instead of by one host thread; the decompressed bytes are the same.
-        Side files stay on the host path; with ``{name}`` or ``output_parts`` > 1 it is a NotImplementedError."""
+        Side files stay on the host path; with ``{name}`` or ``output_parts`` > 1 it is a NotImplementedError.
+
+        ``device_gunzip``: a ``path_in`` that ends in ``.gz`` and holds BGZF members (``bgzip``, htslib,
+        ``device_gzip=True``) is inflated on the GPU, a wave per member, instead of by one host thread; any other
+        input is read as without the flag (``fastq.ChunkedFastqReader``).  It only changes where the text comes
+        from, and combines with every other option."""
         if device_gzip and ("{name}" in path_out or self.demultiplex):
             raise NotImplementedError("device_gzip with demultiplexed outputs ({name} in the output path)")
         if "{name}" not in path_out and not self.demultiplex:
-            return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts, device_gzip=device_gzip)
+            return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts, device_gzip=device_gzip,
+                                device_gunzip=device_gunzip)
         if "{name}" not in path_out:
             raise ValueError("a demultiplexing pipeline needs {name} in the output path")
         if output_parts and int(output_parts) > 1:
@@ -836,7 +844,7 @@ class TrimPipeline(object):
         self.demultiplex = True
         try:
             self._check_demux()                               # before any output is opened
-            return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts)
+            return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts, device_gunzip=device_gunzip)
         finally:
             self.demultiplex = was
 
@@ -1118,19 +1126,20 @@ class PairedTrimPipeline(object):
         return PairedTrimResult(self.p1._result(mates[0], dest), self.p2._result(mates[1], dest), merged_text)
 
     def trim_files(self, in1, in2, out1, out2, chunk_bytes=128 << 20, merged_out=None, keep_output=False, output_parts=1,
-                   device_gzip=False):
+                   device_gzip=False, device_gunzip=False):
         """Stream two FASTQ files through the GPU in lock step (chunks of whole records, the
         same number from each file); returns the destination counts.  ``merged_out``: the
         --merged-output file (without it merged reads are dropped, as by the reference).
         ``output_parts`` > 1: every output as that many part files (``TrimPipeline.trim_file``); part i of
         ``out1`` and part i of ``out2`` hold the same pairs in the same order.  ``device_gzip``: the outputs
-        (all ending in ``.gz``) are compressed on the GPU, as in ``TrimPipeline.trim_file``."""
+        (all ending in ``.gz``) are compressed on the GPU, as in ``TrimPipeline.trim_file``.  ``device_gunzip``: BGZF
+        ``.gz`` inputs are inflated on the GPU, as in ``TrimPipeline.trim_file``."""
         if device_gzip and any(p is not None and "{name}" in str(p) for p in (out1, out2, merged_out)):
             raise NotImplementedError("device_gzip with demultiplexed outputs ({name} in the output path)")
         if any(p is not None and "{name}" in str(p) for p in (out1, out2, merged_out)):
             raise ValueError("Demultiplexing not supported for paired-end files, yet.")        # trim/cli.py:769-771
         return _trim_stream(self, [in1, in2], [out1, out2], chunk_bytes, keep_output, output_parts, merged_out,
-                            device_gzip=device_gzip)
+                            device_gzip=device_gzip, device_gunzip=device_gunzip)
 
     def trim_bytes(self, data1, data2, which=_lib.DEST_KEEP):
         """Two FASTQ texts in (same number of records), the two trimmed texts out."""

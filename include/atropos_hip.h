@@ -871,6 +871,32 @@ int atr_gzip_eof(uint8_t *buf28);                 /* fills the 28 bytes; returns
 int atr_gzip_blocks(const uint8_t *d_text, int64_t n_bytes, uint8_t *d_out, int64_t out_capacity, int64_t *d_total,
                     int64_t *d_member_offsets, void *d_work, void *stream);
 
+/* ---- BGZF .gz input inflated on the device (gunzip_kernels.hip, inflate_core.hpp) ------------------------------------
+ * A BGZF member is a gzip member of at most 64 KiB, compressed and as text, that carries its size in the 'BC' extra
+ * subfield (BSIZE = size - 1) and its text size in the trailer (ISIZE), and whose window never reaches into the member
+ * before it: the members of a stream are inflated independently, each straight to its place in the text.
+ *   atr_bgzf_scan       HOST bytes: walks the whole members at the front of buf[0 .. n_bytes), at most max_members, and
+ *                       fills member_at[0 .. k] (byte offsets) and text_at[0 .. k] (running sum of ISIZE), each of
+ *                       max_members + 1 entries; *n_members = k, *covered = member_at[k].  It stops at the first member
+ *                       that is not whole.  ATR_ERR_INVALID at a header that is no BGZF member -- magic, CM, FEXTRA,
+ *                       no 'BC' subfield, SLEN other than 2, ISIZE above 65 536 --, with *n_members / *covered at it.
+ *   atr_gunzip_members  DEVICE: member m = d_stream[d_member_at[m] .. d_member_at[m + 1]) is checked (header, BSIZE,
+ *                       RFC 1951 in full, ISIZE, CRC-32) and its text written to d_text[d_text_at[m] .. d_text_at[m + 1]).
+ *                       d_stream is readable up to the next multiple of 16 beyond n_stream.  d_status[m]: 0, or which
+ *                       rule the member broke (inflate_core.hpp INF_E_*; the code is informational); d_bad: their
+ *                       number.  A member with a nonzero status leaves its own text range unspecified and touches
+ *                       nothing else; ranges that are none (decreasing, beyond n_stream or text_capacity, above
+ *                       64 KiB) are such a status.
+ * ATR_ERR_INVALID: a negative size, more members than n_stream can hold, a missing pointer; ATR_ERR_UNSUPPORTED:
+ * n_stream or text_capacity >= 4 GiB, n_members > 2^22 (ATR_GUNZIP_MAX_MEMBERS) -- all before any pointer is looked at.
+ * A capacity below d_text_at[n_members] cannot be seen from the host (the offsets are device memory): the members whose
+ * text would not fit get the range status, and nothing of them is stored. */
+#define ATR_GUNZIP_MAX_MEMBERS (1 << 22)
+int atr_bgzf_scan(const uint8_t *buf, int64_t n_bytes, int64_t max_members, int64_t *member_at, int64_t *text_at,
+                  int64_t *n_members, int64_t *covered);
+int atr_gunzip_members(const uint8_t *d_stream, int64_t n_stream, const int64_t *d_member_at, const int64_t *d_text_at,
+                       int64_t n_members, uint8_t *d_text, int64_t text_capacity, int32_t *d_status, int32_t *d_bad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
