@@ -61,6 +61,12 @@ class LinkedAdapterSpec(C.Structure):
 
 LINKED_MAX_ADAPTERS = 4
 
+
+class STREAM(C.c_void_p):
+    """The ``void *stream`` argument of an entry point: a hipStream_t as an integer (0: the null stream).  Where a
+    prototype names it, ``_call`` supplies the current stream; the callers never pass one."""
+
+
 # prototypes of every symbol include/atropos_hip.h declares
 PROTOTYPES = {
     "atr_version": (C.c_int, []),
@@ -69,36 +75,36 @@ PROTOTYPES = {
     "atr_translate_table": (C.c_int, [C.c_int, C.c_char_p]),
     "atr_packed_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "atr_pack_reads": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_char_p,
-                                 C.c_void_p, C.c_void_p, C.c_void_p]),
-    "atr_planes_count_uncoded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+                                 C.c_void_p, C.c_void_p, STREAM]),
+    "atr_planes_count_uncoded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, STREAM]),
     "atr_pack_planes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_char_p,
-                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+                                  C.c_void_p, C.c_void_p, STREAM]),
     "atr_multi_locate_work_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "atr_multi_locate_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                          C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_int, C.c_void_p]),
+                                         C.c_void_p, C.c_int, STREAM]),
     "atr_compare_batch": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
-                                    C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+                                    C.c_int, C.c_int, C.c_int, C.c_void_p, STREAM]),
     "atr_locate_debug_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "atr_locate_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "atr_compare_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "atr_locate_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, STREAM]),
+    "atr_compare_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, STREAM]),
     "atr_adapter_postfilter": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
-                                         C.c_double, C.c_int, C.c_void_p]),
+                                         C.c_double, C.c_int, STREAM]),
     "atr_correct_errors_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
-                                           C.c_int, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                           C.c_int, C.c_char_p, C.c_void_p, C.c_void_p, STREAM]),
     "atr_insert_correct_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_char_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+                                           C.c_void_p, C.c_void_p, STREAM]),
     "atr_insert_match_correct_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                                 C.c_int, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                                 C.c_int, C.c_char_p, C.c_void_p, C.c_void_p, STREAM]),
     "atr_insert_aligner_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "atr_insert_aligner_destroy": (None, [C.c_void_p]),
     "atr_insert_match_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                         C.c_int, C.c_void_p, C.c_void_p]),
+                                         C.c_int, C.c_void_p, STREAM]),
     "atr_insert_match_batch_coded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+                                               C.c_int, C.c_int, C.c_void_p, STREAM]),
     "atr_case_sensitive_table": (C.c_int, [C.c_char_p]),
     "atr_aligner_create": (C.c_int, [C.c_char_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(C.c_void_p)]),
@@ -107,113 +113,113 @@ PROTOTYPES = {
     "atr_aligner_set_indel_cost": (C.c_int, [C.c_void_p, C.c_int]),
     "atr_aligner_query_table": (C.c_int, [C.c_void_p, C.c_char_p]),
     "atr_locate_work_bytes": (C.c_size_t, [C.c_int64]),
-    "atr_locate_work_unresolved": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]),
+    "atr_locate_work_unresolved": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, STREAM, C.POINTER(C.c_int64)]),
     "atr_locate_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                   C.c_void_p, C.c_void_p]),
-    "atr_locate_ascii_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
-    "atr_locate_one": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "atr_insert_match_one": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]),
+                                   C.c_void_p, STREAM]),
+    "atr_locate_ascii_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, STREAM]),
+    "atr_locate_one": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, STREAM]),
+    "atr_insert_match_one": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, STREAM]),
     "atr_multi_locate_one": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
-                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "atr_compare_one": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+                                       C.c_void_p, C.c_int, C.c_void_p, STREAM]),
+    "atr_compare_one": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, STREAM]),
     "atr_locate_planes_applies": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "atr_aligner_prepare": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "atr_locate_ascii_planes_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p]),
-    "atr_locate_planes_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                                C.c_void_p, C.c_void_p, STREAM]),
+    "atr_locate_planes_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, STREAM]),
     "atr_locate_batch_path": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_int, C.c_void_p]),
+                                        C.c_void_p, C.c_int, STREAM]),
     "atr_linked_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "atr_linked_destroy": (None, [C.c_void_p]),
     "atr_linked_query_table": (C.c_int, [C.c_void_p]),
     "atr_linked_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
     "atr_linked_match_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
     "atr_linked_group_applies": (C.c_int, [C.c_void_p, C.c_int]),
     "atr_linked_group_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "atr_linked_group_work_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
     "atr_linked_group_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_char_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+                                        C.POINTER(C.c_int64), C.c_void_p, STREAM]),
     "atr_linked_group_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
     "atr_locate_pairs_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                         C.c_void_p]),
+                                         STREAM]),
     "atr_locate_pairs_need_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                              C.c_void_p, C.c_void_p]),
+                                              C.c_void_p, STREAM]),
     "atr_locate_pairs_path_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                              C.c_int, C.c_void_p, C.c_void_p]),
+                                              C.c_int, C.c_void_p, STREAM]),
     "atr_locate_pairs_long_work_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "atr_locate_pairs_long_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                              C.c_void_p, C.c_void_p]),
+                                              C.c_void_p, STREAM]),
     "atr_locate_pair_one": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
-                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+                                      C.c_int, C.c_int, C.c_void_p, STREAM]),
     "atr_locate_pairs_full_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                              C.c_void_p]),
+                                              STREAM]),
     "atr_fastq_work_bytes": (C.c_size_t, [C.c_int64]),
-    "atr_fastq_count_lines": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "atr_fastq_count_lines": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, STREAM]),
     "atr_fastq_index": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                  C.c_void_p, C.c_void_p]),
+                                  C.c_void_p, STREAM]),
     "atr_pack_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_char_p,
-                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "atr_pair_filter_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
+    "atr_pair_filter_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, STREAM]),
     "atr_insert_plan_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "atr_clip_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
+    "atr_clip_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, STREAM]),
     "atr_quality_trim_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                         C.c_int, C.c_int, C.c_void_p]),
+                                         C.c_int, C.c_int, STREAM]),
     "atr_nend_trim_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_int64, C.c_void_p]),
+                                      C.c_int64, STREAM]),
     "atr_match_trim_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_int64, C.c_void_p]),
+                                       C.c_void_p, C.c_int64, STREAM]),
     "atr_read_filter_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+                                        C.c_void_p, C.c_void_p, STREAM]),
     "atr_merge_work_bytes": (C.c_size_t, [C.c_int64]),
-    "atr_merge_plan_batch": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] + [C.c_void_p] * 5),
-    "atr_merge_emit_batch": (C.c_int, [C.c_void_p] * 11 + [C.c_int64, C.c_int, C.c_int, C.c_char_p] + [C.c_void_p] * 5),
+    "atr_merge_plan_batch": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] + [C.c_void_p] * 4 + [STREAM]),
+    "atr_merge_emit_batch": (C.c_int, [C.c_void_p] * 11 + [C.c_int64, C.c_int, C.c_int, C.c_char_p] + [C.c_void_p] * 4 + [STREAM]),
     "atr_fastq_emit_work_bytes": (C.c_size_t, [C.c_int64]),
     "atr_fastq_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                 C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
     "atr_fastq_emit_grouped_work_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
-    "atr_fastq_emit_grouped": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 5),
-    "atr_demux_groups": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "atr_fastq_emit_grouped": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 4 + [STREAM]),
+    "atr_demux_groups": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64, C.c_void_p, STREAM]),
     "atr_read_stats_bytes": (C.c_int64, [C.c_int]),
-    "atr_read_stats_clear": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "atr_read_stats_clear": (C.c_int, [C.c_void_p, C.c_int, STREAM]),
     "atr_read_stats_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
-                             + [C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
-    "atr_read_stats_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+                             + [C.c_int, C.c_int64, C.c_int64, STREAM]),
+    "atr_read_stats_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, STREAM]),
     "atr_detect_create": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_int, C.POINTER(C.c_void_p)]),
     "atr_detect_destroy": (None, [C.c_void_p]),
     "atr_detect_counter_bytes": (C.c_int64, [C.c_void_p]),
-    "atr_detect_clear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "atr_detect_clear": (C.c_int, [C.c_void_p, C.c_void_p, STREAM]),
     "atr_detect_filter_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]),
-    "atr_detect_mark_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "atr_detect_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p]),
-    "atr_detect_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                          C.c_void_p, STREAM]),
+    "atr_detect_mark_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, STREAM]),
+    "atr_detect_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, STREAM]),
+    "atr_detect_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
     "atr_report_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "atr_report_destroy": (None, [C.c_void_p]),
     "atr_report_counters": (C.c_int64, [C.c_void_p]),
-    "atr_report_intervals": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "atr_report_intervals": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, STREAM]),
     "atr_report_adapters": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
-                                      C.c_void_p, C.c_void_p]),
-    "atr_report_outputs": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p]),
-    "atr_report_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                      C.c_void_p, STREAM]),
+    "atr_report_outputs": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, STREAM]),
+    "atr_report_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
     "atr_gzip_bound": (C.c_int64, [C.c_int64]),
     "atr_gzip_work_bytes": (C.c_size_t, [C.c_int64]),
     "atr_gzip_eof": (C.c_int, [C.c_void_p]),
-    "atr_gzip_blocks": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+    "atr_gzip_blocks": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [STREAM]),
     "atr_bgzf_scan": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4),
-    "atr_gunzip_members": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
+    "atr_gunzip_members": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 2 + [STREAM]),
 }
 GZIP_BLOCK = 65280                       # atr_gzip_blocks: bytes of text per BGZF member
 GUNZIP_MAX_MEMBERS = 1 << 22             # atr_gunzip_members: members of one call (ATR_GUNZIP_MAX_MEMBERS)
@@ -242,6 +248,20 @@ class AtroposUnsupported(AtroposHipError):
     """ATR_ERR_UNSUPPORTED: the request is outside the device kernels' envelope."""
 
 
+def attach_prototypes(lib, prefix="atr_", only=None):
+    """Give the symbols of ``lib`` the restype / argtypes of PROTOTYPES; ``{atr_ name: (function, stream position or
+    None)}``.  The CPU test-suite attaches the same prototypes to the kernels' CPU twins, which export ``emu_x`` with
+    ``atr_x``'s signature (``prefix``, ``only``: the names one twin library stands in for)."""
+    fns = {}
+    for name in PROTOTYPES if only is None else only:
+        res, args = PROTOTYPES[name]
+        fn = getattr(lib, prefix + name[4:])   # AttributeError if a declared symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
+        fns[name] = (fn, args.index(STREAM) if STREAM in args else None)
+    return fns
+
+
 def load_library(path=LIB_PATH):
     """dlopen the C-ABI library and attach prototypes.  Raises if it is missing."""
     if not os.path.exists(path):
@@ -249,15 +269,12 @@ def load_library(path=LIB_PATH):
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C atropos_amd/csrc`). There is no CPU fallback." % path)
     lib = C.CDLL(path)
-    for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
+    attach_prototypes(lib)
     return lib
 
 
 def _check(lib, rc, what):
-    if rc >= 0:
+    if rc is None or rc >= 0:              # (None: a void function)
         return rc
     if rc == -1:
         raise ValueError("%s: invalid argument" % what)
@@ -266,7 +283,7 @@ def _check(lib, rc, what):
     detail = ERRORS.get(rc, "error %d" % rc)
     if rc == -2:
         raise AtroposUnsupported("%s: %s" % (what, detail))
-    if rc == -3:
+    if rc == -3 and lib is not None:
         detail += ": " + (lib.atr_last_error() or b"").decode("ascii", "replace")
     raise AtroposHipError("%s: %s" % (what, detail))
 
@@ -318,21 +335,560 @@ class LinkedGroups(object):
         return [int(self.info[g]) for g in range(LINKED_MAX_ADAPTERS)]
 
 
-class HipBackend(object):
-    """Thin object view of the C ABI; all buffers are torch tensors on one GPU."""
+class AbiCalls(object):
+    """The wrappers of the C ABI that every backend serves: ``HipBackend`` below and the CPU test-suite's stand-in, whose
+    library exports the kernels' CPU twins under the same signatures.  A subclass supplies
+
+      ``device``            where the tensors of a call live,
+      ``empty(shape, dtype)``  an output buffer there,
+      ``_call(name, *args)``   calls entry point ``name`` (its ``atr_`` name) on the current device and stream -- the
+                            stream argument is the subclass's to add, where PROTOTYPES names one -- and raises on an
+                            error code; returns the code otherwise,
+      ``_host(name, *args)``   the same for the entry points that touch no device,
+      ``_symbol(name)``        the bare ctypes function,
+      ``_workspace(need, first=0)``  the kernels' scratch of at least ``need`` bytes, kept between calls (``first``: the
+                            size of a new one when none is kept yet)."""
+
+    def translate_table(self, kind):
+        buf = C.create_string_buffer(256)
+        self._host("atr_translate_table", kind, buf)
+        return buf.raw
+
+    def packed_bytes(self, nreads, max_len):
+        return self._host("atr_packed_bytes", nreads, max_len)
+
+    def pack_reads(self, ascii_2d, lens, max_len, table, count_invalid=False, starts=None, planes=False):
+        """ascii_2d: uint8 [nreads, >=max_len] on self.device (row stride arbitrary);
+        lens: int32 [nreads] or None; starts: int32 [nreads] or None (pack read[start:]);
+        table: 256 bytes; planes: plane64 layout (the insert aligner's) instead of tile64.
+        Returns the packed uint8 tensor (and, with count_invalid, the number of reads
+        holding a byte the table maps to 0)."""
+        nreads = ascii_2d.shape[0]
+        packed = self.empty((max(self.packed_bytes(nreads, max_len), 16),), torch.uint8)
+        invalid = torch.zeros((1,), dtype=torch.int32, device=self.device) if count_invalid else None
+        if nreads and max_len:
+            self._call("atr_pack_planes" if planes else "atr_pack_reads", _ptr(ascii_2d), ascii_2d.stride(0), _ptr(lens),
+                       _ptr(starts), nreads, max_len, table, _ptr(packed), _ptr(invalid))
+        return (packed, int(invalid.item())) if count_invalid else packed
+
+    def planes_count_uncoded(self, planes, lens, other_lens, nreads, max_len):
+        """Number of reads of a plane64 buffer with an uncoded base among their first
+        min(lens, other_lens) bases (atr_planes_count_uncoded); either lens may be None (max_len)."""
+        count = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        if nreads and max_len:
+            self._call("atr_planes_count_uncoded", _ptr(planes), _ptr(lens), _ptr(other_lens), nreads, max_len, _ptr(count))
+        return int(count.item())
+
+    def multi_locate_batch(self, refs, ref_lens, queries, query_lens, e, flags, min_overlap, max_matches,
+                           max_ref_len, out_stride):
+        """refs/queries: uint8 [npairs, width] raw ASCII on the device; returns
+        (records int16 [npairs, out_stride, 8], counts int32 [npairs])."""
+        npairs = refs.shape[0]
+        out = self.empty((npairs, out_stride, 8), torch.int16)
+        counts = self.empty((npairs,), torch.int32)
+        work = self.empty((max(self._host("atr_multi_locate_work_bytes", npairs, max_ref_len), 4),), torch.uint8)
+        if npairs:
+            self._call("atr_multi_locate_batch", _ptr(refs), refs.stride(0), _ptr(ref_lens), _ptr(queries), queries.stride(0),
+                       _ptr(query_lens), npairs, e, flags, min_overlap, max_matches, max_ref_len, _ptr(work), _ptr(out),
+                       _ptr(counts), out_stride)
+        return out, counts
+
+    def compare_batch(self, ref, queries, lens, max_len, wildcard_ref, wildcard_query, suffix):
+        """ref: bytes; queries: uint8 [n, width] raw ASCII on the device."""
+        n = queries.shape[0]
+        out = self.empty((n, 8), torch.int16)
+        if n:
+            self._call("atr_compare_batch", ref, len(ref), _ptr(queries), queries.stride(0), _ptr(lens), n, max_len,
+                       int(wildcard_ref), int(wildcard_query), int(suffix), _ptr(out))
+        return out
+
+    def adapter_postfilter(self, records, m, min_overlap, max_error_rate, rmp, max_rmp, accept_full):
+        """In-place acceptance test of Adapter.match_to on int16 [n, 8] records; rmp: float64
+        [ld, ld] device tensor or None."""
+        if records.shape[0]:
+            self._call("atr_adapter_postfilter", _ptr(records), records.shape[0], m, min_overlap, max_error_rate, _ptr(rmp),
+                       0 if rmp is None else rmp.shape[1], 0.0 if max_rmp is None else max_rmp, int(accept_full))
+        return records
+
+    def correct_errors_batch(self, seq1, qual1, lens1, seq2, qual2, lens2, insert, mask, action, min_qual_diff,
+                             truncate, comp):
+        """In-place error correction of the overlaps (uint8 [n, width] ASCII tensors on
+        the device, same row stride); returns (changed int32 [n, 2], newlen int32 [n, 2])."""
+        n = seq1.shape[0]
+        changed = self.empty((n, 2), torch.int32)
+        newlen = self.empty((n, 2), torch.int32)
+        if n:
+            if seq1.stride(0) != seq2.stride(0):
+                raise ValueError("both reads need the same row stride")
+            self._call("atr_correct_errors_batch", _ptr(seq1), _ptr(qual1), _ptr(lens1), _ptr(seq2), _ptr(qual2), _ptr(lens2),
+                       seq1.stride(0), _ptr(insert), _ptr(mask), n, seq1.shape[1], action, min_qual_diff, int(truncate), comp,
+                       _ptr(changed), _ptr(newlen))
+        return changed, newlen
+
+    def insert_correct_batch(self, records, seq1, qual1, lens1, seq2, qual2, lens2, action, min_qual_diff, comp,
+                             changed=None, newlen=None, planes1=None, planes2=None):
+        """Error correction of the pairs whose insert match (records of insert_match_batch) has
+        errors, in place on uint8 [n, width] ASCII tensors; returns (changed, newlen) int32 [n, 2].
+        planes1 / planes2: the plane64 ReadBatches the records were computed from (optional; the
+        kernel then only visits the positions where the reads disagree)."""
+        n = seq1.shape[0]
+        changed = self.empty((n, 2), torch.int32) if changed is None else changed
+        newlen = self.empty((n, 2), torch.int32) if newlen is None else newlen
+        if n:
+            if seq1.stride(0) != seq2.stride(0):
+                raise ValueError("both reads need the same row stride")
+            self._call("atr_insert_correct_batch", _ptr(records), None if planes1 is None else _ptr(planes1.packed),
+                       None if planes2 is None else _ptr(planes2.packed), 0 if planes1 is None else planes1.max_len,
+                       _ptr(seq1), _ptr(qual1), _ptr(lens1), _ptr(seq2), _ptr(qual2), _ptr(lens2), seq1.stride(0), n,
+                       seq1.shape[1], action, min_qual_diff, comp, _ptr(changed), _ptr(newlen))
+        return changed, newlen
+
+    def insert_aligner_create(self, cfg):
+        h = C.c_void_p()
+        self._call("atr_insert_aligner_create", C.addressof(cfg), C.byref(h))
+        return h
+
+    def insert_aligner_destroy(self, h):
+        self._host("atr_insert_aligner_destroy", h)
+
+    def insert_match_batch(self, h, packed1, lens1, packed2, lens2, npairs, max_len, cased=False):
+        """cased: both reads are packed with ``case_sensitive_table()`` (soft-masked reads)."""
+        out = self.empty((npairs, 3, 8), torch.int16)
+        if npairs:
+            self._call("atr_insert_match_batch_coded", h, _ptr(packed1), _ptr(lens1), _ptr(packed2), _ptr(lens2), npairs, max_len,
+                       1 if cased else 0, _ptr(out))
+        return out
+
+    def case_sensitive_table(self):
+        buf = C.create_string_buffer(256)
+        self._host("atr_case_sensitive_table", buf)
+        return buf.raw
+
+    def aligner_create(self, ref, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost):
+        h = C.c_void_p()
+        self._host("atr_aligner_create", ref, len(ref), e, flags, int(wildcard_ref), int(wildcard_query), min_overlap,
+                   indel_cost, C.byref(h))
+        return h
+
+    def aligner_destroy(self, h):
+        self._host("atr_aligner_destroy", h)
+
+    def aligner_set_min_overlap(self, h, v):
+        self._host("atr_aligner_set_min_overlap", h, v)
+
+    def aligner_set_indel_cost(self, h, v):
+        self._host("atr_aligner_set_indel_cost", h, v)
+
+    def aligner_query_table(self, h):
+        buf = C.create_string_buffer(256)
+        kind = self._host("atr_aligner_query_table", h, buf)
+        return kind, buf.raw
+
+    def locate_batch(self, h, packed, lens, nreads, max_len, filtered=True, path=None):
+        """path: one of LOCATE_PATHS ("auto": the fastest applicable kernels -- a wavefront per read for short
+        batches, the filtered pipeline (bit-parallel pre-pass + windowed DP) for long ones; "full", "filtered",
+        "wave": that kernel family); the records are identical on every path.  ``filtered=False`` is "full"."""
+        if path is None:
+            path = "auto" if filtered else "full"
+        code = LOCATE_PATHS[path]
+        out = self.empty((nreads, 8), torch.int16)
+        if nreads:
+            work = None
+            if code in (0, 2) and (code == 2 or nreads > WAVE_MAX_READS):
+                work = self._workspace(self._host("atr_locate_work_bytes", nreads))
+            elif code == 0:
+                # short batches that do not take the wave kernel: references of more than 64 bases never use the
+                # scratch, anchored prefixes only need it to be there
+                work = self._workspace(0, first=self._host("atr_locate_work_bytes", WAVE_MAX_READS))
+            self._call("atr_locate_batch_path", h, _ptr(packed), _ptr(lens), nreads, max_len, _ptr(out), _ptr(work), code)
+        return out
+
+    def locate_planes_applies(self, h, max_len, ragged=False):
+        """Is this aligner on reads of max_len bases (ragged: of at most max_len) inside the envelope of the
+        two-pass pre-pass (plane64 reads, atr_locate_planes_batch)?"""
+        return bool(self._host("atr_locate_planes_applies", h, int(max_len), int(bool(ragged))))
+
+    def locate_planes_batch(self, h, planes, lens, nreads, max_len):
+        """Batched locate on a plane64 batch (atr_locate_planes_batch); lens None: equal-length reads."""
+        out = self.empty((nreads, 8), torch.int16)
+        if nreads:
+            work = self._workspace(self._host("atr_locate_work_bytes", nreads))
+            self._call("atr_locate_planes_batch", h, _ptr(planes), _ptr(lens), nreads, max_len, _ptr(out), _ptr(work))
+        return out
+
+    # -- linked adapters (one fused pipeline for the whole set) ---------------------
+    def linked_create(self, specs):
+        """specs: list of LinkedAdapterSpec.  Returns the set handle; AtroposHipError
+        ("unsupported") when the set is outside the fused kernels' envelope."""
+        arr = (LinkedAdapterSpec * len(specs))(*specs)
+        h = C.c_void_p()
+        self._call("atr_linked_create", C.addressof(arr), len(specs), C.byref(h))
+        return h
+
+    def linked_destroy(self, h):
+        self._host("atr_linked_destroy", h)
+
+    def linked_match_batch(self, h, packed, lens, nreads, max_len):
+        """(which int8 [n, 2] = (first matching adapter | -1, number of matching 5' parts),
+        front int16 [n, 8], back int16 [n, 8]) -- include/atropos_hip.h, atr_linked_match_batch."""
+        which = self.empty((nreads, 2), torch.int8)
+        front = self.empty((nreads, 8), torch.int16)
+        back = self.empty((nreads, 8), torch.int16)
+        if nreads:
+            work = self._workspace(self._host("atr_linked_work_bytes", h, nreads))
+            self._call("atr_linked_match_batch", h, _ptr(packed), _ptr(lens), nreads, max_len, _ptr(which), _ptr(front),
+                       _ptr(back), _ptr(work))
+        return which, front, back
+
+    def locate_debug(self, h, packed, m, n):
+        """atr_locate_debug: (cost matrix int32 [m + 1, n + 1] on the host, INT32_MIN = not computed; the record)."""
+        work = self.empty((max(self._host("atr_locate_debug_bytes", h, n), 16),), torch.uint8)
+        out = self.empty((1, 8), torch.int16)
+        self._call("atr_locate_debug", h, _ptr(packed), n, _ptr(work), _ptr(out))
+        cells = (m + 1) * (n + 1)
+        return work[:4 * cells].view(torch.int32).reshape(m + 1, n + 1).cpu(), out.cpu()
+
+    def compare_packed(self, h, packed, lens, nreads, max_len, suffix):
+        """atr_compare_packed: compare_prefixes / compare_suffixes of aligner ``h``'s reference against
+        reads packed for it.  int16 [nreads, 8]."""
+        out = self.empty((nreads, 8), torch.int16)
+        if nreads:
+            self._call("atr_compare_packed", h, _ptr(packed), _ptr(lens), nreads, max_len, int(suffix), _ptr(out))
+        return out
+
+    def locate_pairs_batch(self, ref_packed, ref_lens, ref_max_len, revcomp_ref, query_packed, query_lens,
+                           query_max_len, npairs, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost,
+                           need=None, path="auto"):
+        """Aligner.locate with a per-pair reference; both sides tile64-packed.  int16 [npairs, 8].
+        need: int32 [npairs] or None -- alignments with fewer matches may come back as None
+        (atr_locate_pairs_need_batch).  path: PAIRS_PATHS ("auto": a wavefront per pair for short batches, the
+        cost / threat / band pipeline or the full sweep for long ones; "full", "fast", "wave": that family)."""
+        out = self.empty((npairs, 8), torch.int16)
+        self._call("atr_locate_pairs_path_batch", _ptr(ref_packed), _ptr(ref_lens), ref_max_len, int(revcomp_ref),
+                   _ptr(query_packed), _ptr(query_lens), query_max_len, npairs, e, flags, int(wildcard_ref),
+                   int(wildcard_query), min_overlap, indel_cost, _ptr(need), PAIRS_PATHS[path], _ptr(out))
+        return out
+
+    def locate_pairs_long_batch(self, ref_packed, ref_lens, ref_max_len, revcomp_ref, query_packed, query_lens,
+                                query_max_len, npairs, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost):
+        """Pairs with a side beyond PAIRS_MAX_LEN (atr_locate_pairs_long_batch: 64-bit cells, the DP column in a
+        workspace allocated here).  The caller keeps npairs * ref_max_len small (PairAligner chunks)."""
+        out = self.empty((npairs, 8), torch.int16)
+        if npairs:
+            work = self.empty((max(self._host("atr_locate_pairs_long_work_bytes", npairs, ref_max_len), 16),), torch.uint8)
+            self._call("atr_locate_pairs_long_batch", _ptr(ref_packed), _ptr(ref_lens), ref_max_len, int(revcomp_ref),
+                       _ptr(query_packed), _ptr(query_lens), query_max_len, npairs, e, flags, int(wildcard_ref),
+                       int(wildcard_query), min_overlap, indel_cost, _ptr(out), _ptr(work))
+        return out
+
+    def locate_pairs_full_batch(self, ref_packed, ref_lens, ref_max_len, revcomp_ref, query_packed, query_lens,
+                                query_max_len, npairs, e, flags, min_overlap, indel_cost):
+        """The same records by the full-matrix sweep alone (atr_locate_pairs_full_batch)."""
+        out = self.empty((npairs, 8), torch.int16)
+        self._call("atr_locate_pairs_full_batch", _ptr(ref_packed), _ptr(ref_lens), ref_max_len, int(revcomp_ref),
+                   _ptr(query_packed), _ptr(query_lens), query_max_len, npairs, e, flags, 0, 0, min_overlap, indel_cost,
+                   _ptr(out))
+        return out
+
+    # -- device-resident FASTQ batch --------------------------------------------
+    def fastq_index(self, data, nbytes):
+        """data: uint8 device tensor holding nbytes of FASTQ text (16-byte aligned, readable up
+        to the next multiple of 16).  Returns (records uint32 [nrec, 8], nlines, error word)."""
+        work = self.empty((max(self._host("atr_fastq_work_bytes", nbytes), 16),), torch.uint8)
+        info = self.empty((2,), torch.int64)
+        self._call("atr_fastq_count_lines", _ptr(data), nbytes, _ptr(work), _ptr(info))
+        nlines = int(info[0].item())
+        line_ends = self.empty((max(nlines, 1),), torch.int32)
+        records = self.empty((nlines // 4, 8), torch.int32)
+        self._call("atr_fastq_index", _ptr(data), nbytes, _ptr(work), _ptr(line_ends), nlines, _ptr(records),
+                   C.c_void_p(info.data_ptr() + 8))
+        return records, line_ends, nlines, int(info[1].item())
+
+    def pack_records(self, data, records, begin, end, max_len, table, count_invalid=False, planes=False):
+        n = records.shape[0]
+        packed = self.empty((max(self.packed_bytes(n, max_len), 16),), torch.uint8)
+        lens = self.empty((n,), torch.int32)
+        invalid = torch.zeros((1,), dtype=torch.int32, device=self.device) if count_invalid else None
+        if n:
+            self._call("atr_pack_records", _ptr(data), _ptr(records), _ptr(begin), _ptr(end), n, max_len, table, int(planes),
+                       _ptr(packed), _ptr(lens), _ptr(invalid))
+        return (packed, lens, int(invalid.item())) if count_invalid else (packed, lens)
+
+    def clip_batch(self, records, begin, end, front, back):
+        self._call("atr_clip_batch", _ptr(records), _ptr(begin), _ptr(end), begin.shape[0], front, back)
+
+    def quality_trim_batch(self, data, records, begin, end, cutoff_front, cutoff_back, base, nextseq):
+        self._call("atr_quality_trim_batch", _ptr(data), _ptr(records), _ptr(begin), _ptr(end), begin.shape[0], cutoff_front,
+                   cutoff_back, base, int(nextseq))
+
+    def nend_trim_batch(self, data, records, begin, end, ubegin=None, uend=None):
+        self._call("atr_nend_trim_batch", _ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend),
+                   begin.shape[0])
+
+    def match_trim_batch(self, matches, front, default_front, begin, end, active, matched):
+        self._call("atr_match_trim_batch", _ptr(matches), _ptr(front), default_front, _ptr(begin), _ptr(end), _ptr(active),
+                   _ptr(matched), begin.shape[0])
+
+    def read_filter_batch(self, data, records, begin, end, ubegin, uend, matched, min_len, max_len, max_n,
+                          discard_trimmed, discard_untrimmed, masks=False):
+        """The destination byte per read, or (masks=True) the bit mask of the filters that fire."""
+        out = self.empty((begin.shape[0],), torch.uint8)
+        self._call("atr_read_filter_batch", _ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend),
+                   _ptr(matched), begin.shape[0], min_len, max_len, max_n, int(discard_trimmed), int(discard_untrimmed),
+                   None if masks else _ptr(out), _ptr(out) if masks else None)
+        return out
+
+    def pair_filter_batch(self, mask1, mask2, min_affected):
+        dest = self.empty((mask1.shape[0],), torch.uint8)
+        self._call("atr_pair_filter_batch", _ptr(mask1), _ptr(mask2), mask1.shape[0], min_affected, _ptr(dest))
+        return dest
+
+    def insert_plan_batch(self, insert, fb1, fb2, batch1, batch2, begin1, end1, begin2, end2, uend1, uend2,
+                          min_insert_len, symmetric, trim_action, correct_action=-1, min_qual_difference=1, comp=None):
+        """InsertAdapterCutter's decision logic (+ optional in-place error correction of the two
+        FASTQ chunks).  Returns (matched1, matched2, corrected int32 [n, 2], error word)."""
+        n = begin1.shape[0]
+        m1, m2 = self.empty((n,), torch.uint8), self.empty((n,), torch.uint8)
+        corrected = self.empty((n, 2), torch.int32)
+        err = self.empty((1,), torch.int64)
+        self._call("atr_insert_plan_batch", _ptr(insert), _ptr(fb1), _ptr(fb2), _ptr(batch1.data), _ptr(batch1.records),
+                   _ptr(batch2.data), _ptr(batch2.records), _ptr(begin1), _ptr(end1), _ptr(begin2), _ptr(end2), _ptr(uend1),
+                   _ptr(uend2), n, min_insert_len, int(symmetric), trim_action, correct_action, min_qual_difference, comp,
+                   _ptr(m1), _ptr(m2), _ptr(corrected), _ptr(err))
+        return m1, m2, corrected, int(err.item())
+
+    def merge_batch(self, align, need, insert_matched, batch1, batch2, begin1, end1, begin2, end2, correct_action=-1,
+                    min_qual_difference=1, comp=None):
+        """MergeOverlapping after the alignments (atr_merge_plan_batch + atr_merge_emit_batch): returns
+        (kind uint8 [n] -- 0: the pair stays a pair --, the FASTQ text of the merged reads in input order,
+        corrected int32 [n, 2], error word).  With a mismatch action the two chunks are corrected in place."""
+        n = begin1.shape[0]
+        kind = self.empty((n,), torch.uint8)
+        offsets = self.empty((n + 1,), torch.int64)
+        corrected = self.empty((n, 2), torch.int32)
+        corrected.zero_()
+        err = self.empty((1,), torch.int64)
+        work = self.empty((max(self._host("atr_merge_work_bytes", n), 16),), torch.uint8)
+        self._call("atr_merge_plan_batch", _ptr(align), _ptr(need), _ptr(batch1.records), _ptr(begin1), _ptr(end1),
+                   _ptr(begin2), _ptr(end2), n, _ptr(kind), _ptr(offsets), _ptr(work), _ptr(err))
+        total = int(offsets[n].item())
+        out = self.empty((max(total, 1),), torch.uint8)
+        if total and int(err.item()) == INT64_MAX:
+            self._call("atr_merge_emit_batch", _ptr(align), _ptr(kind), _ptr(insert_matched), _ptr(batch1.data),
+                       _ptr(batch1.records), _ptr(batch2.data), _ptr(batch2.records), _ptr(begin1), _ptr(end1), _ptr(begin2),
+                       _ptr(end2), n, correct_action, min_qual_difference, comp, _ptr(offsets), _ptr(corrected), _ptr(err),
+                       _ptr(out))
+        return kind, out[:total], corrected, int(err.item())
+
+    def fastq_emit(self, data, records, begin, end, ubegin, uend, dest, which):
+        """Formatted FASTQ text (uint8 device tensor) of the records with dest == which."""
+        n = records.shape[0]
+        offsets = self.empty((n + 1,), torch.int64)
+        work = self.empty((max(self._host("atr_fastq_emit_work_bytes", n), 16),), torch.uint8)
+        hint = int(data.numel() // max(n, 1))
+        args = (_ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(dest), which, n, hint,
+                _ptr(offsets), _ptr(work))
+        self._call("atr_fastq_emit", *args, None)
+        total = int(offsets[n].item())
+        out = self.empty((max(total, 1),), torch.uint8)
+        if total:
+            self._call("atr_fastq_emit", *args, _ptr(out))
+        return out[:total]
+
+    def fastq_emit_grouped(self, data, records, begin, end, ubegin, uend, group, n_groups):
+        """atr_fastq_emit for ``n_groups`` outputs in one pass: (text, bounds) -- the formatted records with
+        ``group[r]`` (int32) == 0 first, then those of group 1 ..., input order inside a group, as one uint8 device
+        tensor, and the ``n_groups + 1`` segment boundaries as a list of ints.  Records with any other code are not
+        written."""
+        n = records.shape[0]
+        n_groups = int(n_groups)
+        if n_groups > EMIT_MAX_GROUPS:
+            raise AtroposUnsupported("atr_fastq_emit_grouped: %d outputs (at most %d)" % (n_groups, EMIT_MAX_GROUPS))
+        offsets = self.empty((max(n, 1),), torch.int64)
+        bounds = self.empty((max(n_groups, 0) + 1,), torch.int64)
+        work = self.empty((max(self._host("atr_fastq_emit_grouped_work_bytes", n, n_groups), 16),), torch.uint8)
+        hint = int(data.numel() // max(n, 1))
+        args = (_ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(group), n_groups, n, hint,
+                _ptr(offsets), _ptr(bounds), _ptr(work))
+        self._call("atr_fastq_emit_grouped", *args, None)
+        edges = bounds.cpu().tolist()
+        out = self.empty((max(edges[-1], 1),), torch.uint8)
+        if edges[-1]:
+            self._call("atr_fastq_emit_grouped", *args, _ptr(out))
+        return out[:edges[-1]], edges
+
+    def demux_groups(self, dest, matched, last_which, adapter_group, n_adapters, untrimmed_group):
+        """The output code of every read of a demultiplexed run (atr_demux_groups): int32 device tensor."""
+        n = dest.shape[0]
+        group = self.empty((n,), torch.int32)
+        self._call("atr_demux_groups", _ptr(dest), _ptr(matched), _ptr(last_which), _ptr(adapter_group), int(n_adapters),
+                   int(untrimmed_group), n, _ptr(group))
+        return group
+
+    # -- .gz output on the device (atr_gzip_*) ------------------------------------------------------------------
+    def gzip_bound(self, nbytes):
+        return self._host("atr_gzip_bound", int(nbytes))
+
+    def gzip_blocks(self, text, offsets=False):
+        """``text`` (uint8 device tensor) as a stream of BGZF members, one per ``GZIP_BLOCK`` bytes: (stream, total) --
+        a uint8 device tensor whose first ``total`` bytes are the members in input order -- and with ``offsets`` also
+        the int64 device tensor of the member starts followed by the total.  Reading ``total`` waits for the kernels."""
+        n = int(text.numel())
+        if not text.is_contiguous():
+            text = text.contiguous()
+        cap = self.gzip_bound(n)
+        out = self.empty((max(cap, 1),), torch.uint8)
+        total = self.empty((1,), torch.int64)
+        starts = self.empty(((n + GZIP_BLOCK - 1) // GZIP_BLOCK + 1,), torch.int64) if offsets else None
+        work = self.empty((max(self._host("atr_gzip_work_bytes", n), 16),), torch.uint8)
+        self._call("atr_gzip_blocks", _ptr(text), n, _ptr(out), cap, _ptr(total), _ptr(starts), _ptr(work))
+        size = int(total.item())
+        return (out, size, starts) if offsets else (out, size)
+
+    # -- BGZF .gz input on the device (atr_bgzf_scan, atr_gunzip_members) ------------------------------------------
+    def bgzf_scan(self, buf, lo, hi, max_members):
+        """The whole BGZF members at the front of ``buf[lo:hi]`` (a uint8 HOST tensor), at most ``max_members``:
+        (member_at, text_at, k, covered, ok) -- int64 host tensors whose entries 0 .. k are the members' offsets from
+        ``lo`` and the running sum of their text sizes; ``covered`` = member_at[k]; ``ok`` is False when the walk
+        stopped at a header that is no BGZF member (at ``lo + covered``)."""
+        return _bgzf_scan(self._symbol("atr_bgzf_scan"), buf, lo, hi, max_members)
+
+    def gunzip_members(self, stream, n_stream, member_at, text_at, n_members, text, capacity):
+        """Inflate ``n_members`` BGZF members of ``stream`` (uint8 device tensor, readable to the next multiple of 16
+        beyond ``n_stream``) into ``text[text_at[m]:text_at[m + 1]]``; ``member_at`` / ``text_at``: int64 device
+        tensors.  Returns (status int32 [n_members], bad int32 [1]) on the device: nothing here waits for the kernel."""
+        status = self.empty((max(int(n_members), 1),), torch.int32)
+        bad = self.empty((1,), torch.int32)
+        self._call("atr_gunzip_members", _ptr(stream), int(n_stream), _ptr(member_at), _ptr(text_at), int(n_members),
+                   _ptr(text), int(capacity), _ptr(status), _ptr(bad))
+        return status, bad
+
+    # -- known-contaminant detection (atr_detect_*) ---------------------------------------------------------------
+    def detect_create(self, seqs, kmer_size, past_end_bases, thresholds, complexity, max_len):
+        """seqs: list of bytes; thresholds: list of int (-1 = never); complexity: float64 ndarray
+        [max_len + 1, max_len + 1].  Returns the handle."""
+        lens = np.asarray([len(s) for s in seqs], dtype=np.int32)
+        thr = np.asarray(thresholds, dtype=np.int32)
+        cx = np.ascontiguousarray(complexity, dtype=np.float64)
+        h = C.c_void_p()
+        self._call("atr_detect_create", b"".join(seqs), lens.ctypes.data, len(seqs), int(kmer_size), bytes(past_end_bases),
+                   len(past_end_bases), thr.ctypes.data, cx.ctypes.data, int(max_len), C.byref(h))
+        return h
+
+    def detect_destroy(self, h):
+        self._host("atr_detect_destroy", h)
+
+    def detect_counters(self, h):
+        """A zeroed counter block (int64 tensor; the words are uint64 counters)."""
+        block = self.empty((self._host("atr_detect_counter_bytes", h) // 8,), torch.int64)
+        self._call("atr_detect_clear", h, _ptr(block))
+        return block
+
+    def detect_filter(self, h, data, records, longest, counters):
+        """(kept int32 [n], hashes int64 [n]) of the records."""
+        n = records.shape[0]
+        kept = self.empty((n,), torch.int32)
+        hashes = self.empty((n,), torch.int64)
+        self._call("atr_detect_filter_batch", h, _ptr(data), _ptr(records), n, int(longest), _ptr(kept), _ptr(hashes),
+                   _ptr(counters))
+        return kept, hashes
+
+    def detect_mark(self, h, data, records, kept, order, head, counters):
+        """rep uint8 [m]: 1 for one read of every distinct kept sequence (order / head: int64 [m])."""
+        m = order.shape[0]
+        rep = self.empty((m,), torch.uint8)
+        self._call("atr_detect_mark_batch", h, _ptr(data), _ptr(records), _ptr(kept), _ptr(order), _ptr(head), m, _ptr(rep),
+                   _ptr(counters))
+        return rep
+
+    def detect_match(self, h, data, records, kept, order, rep, counters):
+        self._call("atr_detect_batch", h, _ptr(data), _ptr(records), _ptr(kept), _ptr(order), _ptr(rep), order.shape[0],
+                   _ptr(counters))
+
+    def detect_read(self, h, counters):
+        """The counter block as a host int64 ndarray."""
+        out = np.zeros((counters.shape[0],), dtype=np.int64)
+        self._call("atr_detect_read", h, _ptr(counters), out.ctypes.data)
+        return out
+
+    # -- the trim report (atr_report_*) ---------------------------------------------------------------------------
+    def report_create(self, n_adapters, max_read_len, max_errors):
+        h = C.c_void_p()
+        self._host("atr_report_create", int(n_adapters), int(max_read_len), int(max_errors), C.byref(h))
+        return h
+
+    def report_destroy(self, h):
+        self._host("atr_report_destroy", h)
+
+    def report_counters(self, h):
+        """A zeroed counter block (int64 tensor) for the handle's layout."""
+        return torch.zeros((self._host("atr_report_counters", h),), dtype=torch.int64, device=self.device)
+
+    def report_intervals(self, h, records, begin0, end0, begin1, end1, mode, front, back, slot, counters):
+        self._call("atr_report_intervals", h, _ptr(records), _ptr(begin0), _ptr(end0), _ptr(begin1), _ptr(end1),
+                   begin0.shape[0], int(mode), int(front), int(back), int(slot), _ptr(counters))
+
+    def report_adapters(self, h, data, records, took, best, which, front, default_front, begin, end, longest, weight,
+                        variant, counters):
+        self._call("atr_report_adapters", h, _ptr(data), _ptr(records), _ptr(took), _ptr(best), _ptr(which), _ptr(front),
+                   int(default_front), _ptr(begin), _ptr(end), begin.shape[0], int(longest), int(weight), int(variant),
+                   _ptr(counters))
+
+    def report_outputs(self, h, records, begin, end, matched, dest, counters):
+        self._call("atr_report_outputs", h, _ptr(records), _ptr(begin), _ptr(end), _ptr(matched), _ptr(dest), begin.shape[0],
+                   _ptr(counters))
+
+    def report_read(self, h, counters):
+        """The counter block as a host int64 ndarray (the one device -> host copy of a report)."""
+        out = np.zeros((counters.shape[0],), dtype=np.int64)
+        self._call("atr_report_read", h, _ptr(counters), out.ctypes.data)
+        return out
+
+
+class HipBackend(AbiCalls):
+    """Thin object view of the C ABI; all buffers are torch tensors on one GPU.  The calls the CPU test-suite's stand-in
+    serves as well are ``AbiCalls``'; here are the plumbing under them and the device-only calls."""
 
     name = "hip"
+    WORKS_KEPT = 4
 
     def __init__(self, device=None):
         self.lib = load_library()
+        self._fns = attach_prototypes(self.lib)
         if not torch.cuda.is_available():
             raise AtroposHipError("no HIP device visible to torch; the alignment kernels need an MI355X")
-        ndev = _check(self.lib, self.lib.atr_device_count(), "atr_device_count")
-        if ndev < 1:
+        if self._host("atr_device_count") < 1:
             raise AtroposHipError("atr_device_count() == 0: no HIP device")
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self._works = {}                  # the kernels' scratch, one per stream calls are issued on (Aligner.locate_stream)
         self._side = []
+
+    # -- the call path -----------------------------------------------------------
+    def _call(self, name, *args):
+        """Entry point ``name`` on this backend's device, on the current stream where the prototype has one."""
+        fn, at = self._fns[name]
+        with torch.cuda.device(self.device):
+            if at is None:
+                rc = fn(*args)
+            else:
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                rc = fn(*args, stream) if at == len(args) else fn(*args[:at], stream, *args[at:])
+        return rc if rc is None or rc >= 0 else _check(self.lib, rc, name)
+
+    def _host(self, name, *args):
+        """An entry point that touches no device: no device guard, no stream."""
+        rc = self._fns[name][0](*args)
+        return rc if rc is None or rc >= 0 else _check(self.lib, rc, name)
+
+    def _symbol(self, name):
+        return self._fns[name][0]
+
+    def _stream(self):
+        """The current stream as an argument for a direct call of a library function (tests, tools)."""
+        return STREAM(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def empty(self, shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=self.device)
 
     @property
     def _work(self):
@@ -351,7 +907,11 @@ class HipBackend(object):
         while len(self._works) > self.WORKS_KEPT:
             self._works.pop(next(iter(self._works)))
 
-    WORKS_KEPT = 4
+    def _workspace(self, need, first=0):
+        work = self._work
+        if work is None or work.numel() < need:
+            work = self._work = self.empty((max(need, first),), torch.uint8)
+        return work
 
     def last_unresolved(self, nreads, n_adapters=1):
         """Reads the pre-pass of the last filtered call on the current stream left to the exact DP kernels
@@ -360,9 +920,7 @@ class HipBackend(object):
         if work is None:
             return None
         out = C.c_int64(0)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_locate_work_unresolved(_ptr(work), int(nreads), int(n_adapters), self._stream(),
-                                                                  C.byref(out)), "atr_locate_work_unresolved")
+        self._call("atr_locate_work_unresolved", _ptr(work), int(nreads), int(n_adapters), C.byref(out))
         return int(out.value)
 
     def stage_host_bytes(self, mat):
@@ -387,7 +945,6 @@ class HipBackend(object):
             self._side.append(torch.cuda.Stream(device=self.device))
         return self._side[:count]
 
-    # -- helpers ---------------------------------------------------------------
     @contextlib.contextmanager
     def worker_context(self):
         """Device + a stream of its own for a host thread that drives this GPU next to other
@@ -397,144 +954,7 @@ class HipBackend(object):
             yield stream
             stream.synchronize()
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def empty(self, shape, dtype):
-        return torch.empty(shape, dtype=dtype, device=self.device)
-
-    # -- C ABI -----------------------------------------------------------------
-    def translate_table(self, kind):
-        buf = C.create_string_buffer(256)
-        _check(self.lib, self.lib.atr_translate_table(kind, buf), "atr_translate_table")
-        return buf.raw
-
-    def packed_bytes(self, nreads, max_len):
-        return self.lib.atr_packed_bytes(nreads, max_len)
-
-    def pack_reads(self, ascii_2d, lens, max_len, table, count_invalid=False, starts=None, planes=False):
-        """ascii_2d: uint8 [nreads, >=max_len] on self.device (row stride arbitrary);
-        lens: int32 [nreads] or None; starts: int32 [nreads] or None (pack read[start:]);
-        table: 256 bytes; planes: plane64 layout (the insert aligner's) instead of tile64.
-        Returns the packed uint8 tensor (and, with count_invalid, the number of reads
-        holding a byte the table maps to 0)."""
-        nreads = ascii_2d.shape[0]
-        packed = self.empty((max(self.packed_bytes(nreads, max_len), 16),), torch.uint8)
-        invalid = torch.zeros((1,), dtype=torch.int32, device=self.device) if count_invalid else None
-        if nreads and max_len:
-            with torch.cuda.device(self.device):
-                fn = self.lib.atr_pack_planes if planes else self.lib.atr_pack_reads
-                _check(self.lib, fn(_ptr(ascii_2d), ascii_2d.stride(0), _ptr(lens), _ptr(starts), nreads, max_len, table,
-                                    _ptr(packed), _ptr(invalid), self._stream()), "atr_pack_reads")
-        return (packed, int(invalid.item())) if count_invalid else packed
-
-    def planes_count_uncoded(self, planes, lens, other_lens, nreads, max_len):
-        """Number of reads of a plane64 buffer with an uncoded base among their first
-        min(lens, other_lens) bases (atr_planes_count_uncoded); either lens may be None (max_len)."""
-        count = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        if nreads and max_len:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_planes_count_uncoded(_ptr(planes), _ptr(lens), _ptr(other_lens), nreads, max_len,
-                                                                   _ptr(count), self._stream()), "atr_planes_count_uncoded")
-        return int(count.item())
-
-    def multi_locate_batch(self, refs, ref_lens, queries, query_lens, e, flags, min_overlap, max_matches,
-                           max_ref_len, out_stride):
-        """refs/queries: uint8 [npairs, width] raw ASCII on the device; returns
-        (records int16 [npairs, out_stride, 8], counts int32 [npairs])."""
-        npairs = refs.shape[0]
-        out = self.empty((npairs, out_stride, 8), torch.int16)
-        counts = self.empty((npairs,), torch.int32)
-        work = self.empty((max(self.lib.atr_multi_locate_work_bytes(npairs, max_ref_len), 4),), torch.uint8)
-        if npairs:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_multi_locate_batch(
-                    _ptr(refs), refs.stride(0), _ptr(ref_lens), _ptr(queries), queries.stride(0), _ptr(query_lens),
-                    npairs, e, flags, min_overlap, max_matches, max_ref_len, _ptr(work), _ptr(out), _ptr(counts),
-                    out_stride, self._stream()), "atr_multi_locate_batch")
-        return out, counts
-
-    def compare_batch(self, ref, queries, lens, max_len, wildcard_ref, wildcard_query, suffix):
-        """ref: bytes; queries: uint8 [n, width] raw ASCII on the device."""
-        n = queries.shape[0]
-        out = self.empty((n, 8), torch.int16)
-        if n:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_compare_batch(ref, len(ref), _ptr(queries), queries.stride(0), _ptr(lens),
-                                                            n, max_len, int(wildcard_ref), int(wildcard_query),
-                                                            int(suffix), _ptr(out), self._stream()),
-                       "atr_compare_batch")
-        return out
-
-    def adapter_postfilter(self, records, m, min_overlap, max_error_rate, rmp, max_rmp, accept_full):
-        """In-place acceptance test of Adapter.match_to on int16 [n, 8] records; rmp: float64
-        [ld, ld] device tensor or None."""
-        if records.shape[0]:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_adapter_postfilter(
-                    _ptr(records), records.shape[0], m, min_overlap, max_error_rate, _ptr(rmp),
-                    0 if rmp is None else rmp.shape[1], 0.0 if max_rmp is None else max_rmp, int(accept_full),
-                    self._stream()), "atr_adapter_postfilter")
-        return records
-
-    def correct_errors_batch(self, seq1, qual1, lens1, seq2, qual2, lens2, insert, mask, action, min_qual_diff,
-                             truncate, comp):
-        """In-place error correction of the overlaps (uint8 [n, width] ASCII tensors on
-        the device, same row stride); returns (changed int32 [n, 2], newlen int32 [n, 2])."""
-        n = seq1.shape[0]
-        changed = self.empty((n, 2), torch.int32)
-        newlen = self.empty((n, 2), torch.int32)
-        if n:
-            if seq1.stride(0) != seq2.stride(0):
-                raise ValueError("both reads need the same row stride")
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_correct_errors_batch(
-                    _ptr(seq1), _ptr(qual1), _ptr(lens1), _ptr(seq2), _ptr(qual2), _ptr(lens2), seq1.stride(0),
-                    _ptr(insert), _ptr(mask), n, seq1.shape[1], action, min_qual_diff, int(truncate), comp,
-                    _ptr(changed), _ptr(newlen), self._stream()), "atr_correct_errors_batch")
-        return changed, newlen
-
-    def insert_correct_batch(self, records, seq1, qual1, lens1, seq2, qual2, lens2, action, min_qual_diff, comp,
-                             changed=None, newlen=None, planes1=None, planes2=None):
-        """Error correction of the pairs whose insert match (records of insert_match_batch) has
-        errors, in place on uint8 [n, width] ASCII tensors; returns (changed, newlen) int32 [n, 2].
-        planes1 / planes2: the plane64 ReadBatches the records were computed from (optional; the
-        kernel then only visits the positions where the reads disagree)."""
-        n = seq1.shape[0]
-        changed = self.empty((n, 2), torch.int32) if changed is None else changed
-        newlen = self.empty((n, 2), torch.int32) if newlen is None else newlen
-        if n:
-            if seq1.stride(0) != seq2.stride(0):
-                raise ValueError("both reads need the same row stride")
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_insert_correct_batch(
-                    _ptr(records), None if planes1 is None else _ptr(planes1.packed),
-                    None if planes2 is None else _ptr(planes2.packed), 0 if planes1 is None else planes1.max_len,
-                    _ptr(seq1), _ptr(qual1), _ptr(lens1), _ptr(seq2), _ptr(qual2), _ptr(lens2),
-                    seq1.stride(0), n, seq1.shape[1], action, min_qual_diff, comp, _ptr(changed), _ptr(newlen),
-                    self._stream()), "atr_insert_correct_batch")
-        return changed, newlen
-
-    def insert_aligner_create(self, cfg):
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_insert_aligner_create(C.addressof(cfg), C.byref(h)),
-                   "atr_insert_aligner_create")
-        return h
-
-    def insert_aligner_destroy(self, h):
-        self.lib.atr_insert_aligner_destroy(h)
-
-    def insert_match_batch(self, h, packed1, lens1, packed2, lens2, npairs, max_len, cased=False):
-        """cased: both reads are packed with ``case_sensitive_table()`` (soft-masked reads)."""
-        out = self.empty((npairs, 3, 8), torch.int16)
-        if npairs:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_insert_match_batch_coded(
-                    h, _ptr(packed1), _ptr(lens1), _ptr(packed2), _ptr(lens2), npairs, max_len, 1 if cased else 0, _ptr(out),
-                    self._stream()), "atr_insert_match_batch_coded")
-        return out
-
+    # -- device-only calls ---------------------------------------------------------
     def insert_match_correct_batch(self, h, planes1, planes2, seq1, qual1, seq2, qual2, action, min_qual_diff, comp,
                                    changed=None, newlen=None):
         """insert_match_batch + insert_correct_batch as ONE kernel (atr_insert_match_correct_batch): the reads'
@@ -549,74 +969,19 @@ class HipBackend(object):
         changed = self.empty((n, 2), torch.int32) if changed is None else changed
         newlen = self.empty((n, 2), torch.int32) if newlen is None else newlen
         if n:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_insert_match_correct_batch(
-                    h, _ptr(planes1.packed), _ptr(planes1.lens), _ptr(planes2.packed), _ptr(planes2.lens), n, planes1.max_len,
-                    _ptr(out), _ptr(seq1), _ptr(qual1), _ptr(seq2), _ptr(qual2), seq1.stride(0), action, min_qual_diff, comp,
-                    _ptr(changed), _ptr(newlen), self._stream()), "atr_insert_match_correct_batch")
+            self._call("atr_insert_match_correct_batch", h, _ptr(planes1.packed), _ptr(planes1.lens), _ptr(planes2.packed),
+                       _ptr(planes2.lens), n, planes1.max_len, _ptr(out), _ptr(seq1), _ptr(qual1), _ptr(seq2), _ptr(qual2),
+                       seq1.stride(0), action, min_qual_diff, comp, _ptr(changed), _ptr(newlen))
         return out, changed, newlen
-
-    def case_sensitive_table(self):
-        buf = C.create_string_buffer(256)
-        _check(self.lib, self.lib.atr_case_sensitive_table(buf), "atr_case_sensitive_table")
-        return buf.raw
-
-    def aligner_create(self, ref, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost):
-        h = C.c_void_p()
-        _check(self.lib, self.lib.atr_aligner_create(ref, len(ref), e, flags, int(wildcard_ref),
-                                                     int(wildcard_query), min_overlap, indel_cost, C.byref(h)),
-               "atr_aligner_create")
-        return h
-
-    def aligner_destroy(self, h):
-        self.lib.atr_aligner_destroy(h)
-
-    def aligner_set_min_overlap(self, h, v):
-        _check(self.lib, self.lib.atr_aligner_set_min_overlap(h, v), "atr_aligner_set_min_overlap")
-
-    def aligner_set_indel_cost(self, h, v):
-        _check(self.lib, self.lib.atr_aligner_set_indel_cost(h, v), "atr_aligner_set_indel_cost")
-
-    def aligner_query_table(self, h):
-        buf = C.create_string_buffer(256)
-        kind = _check(self.lib, self.lib.atr_aligner_query_table(h, buf), "atr_aligner_query_table")
-        return kind, buf.raw
-
-    def locate_batch(self, h, packed, lens, nreads, max_len, filtered=True, path=None):
-        """path: one of LOCATE_PATHS ("auto": the fastest applicable kernels -- a wavefront per read for short
-        batches, the filtered pipeline (bit-parallel pre-pass + windowed DP) for long ones; "full", "filtered",
-        "wave": that kernel family); the records are identical on every path.  ``filtered=False`` is "full"."""
-        if path is None:
-            path = "auto" if filtered else "full"
-        code = LOCATE_PATHS[path]
-        out = self.empty((nreads, 8), torch.int16)
-        if nreads:
-            work = None
-            if code in (0, 2) and (code == 2 or nreads > WAVE_MAX_READS):
-                need = self.lib.atr_locate_work_bytes(nreads)
-                if self._work is None or self._work.numel() < need:
-                    self._work = self.empty((need,), torch.uint8)
-                work = self._work
-            elif code == 0:
-                work = self._work if self._work is not None else self._small_work()
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_locate_batch_path(h, _ptr(packed), _ptr(lens), nreads, max_len, _ptr(out),
-                                                                _ptr(work), code, self._stream()), "atr_locate_batch")
-        return out
-
-    def locate_planes_applies(self, h, max_len, ragged=False):
-        """Is this aligner on reads of max_len bases (ragged: of at most max_len) inside the envelope of the
-        two-pass pre-pass (plane64 reads, atr_locate_planes_batch)?"""
-        return bool(self.lib.atr_locate_planes_applies(h, int(max_len), int(bool(ragged))))
 
     def aligner_prepare(self, h, max_len, ragged=False):
         """atr_aligner_prepare: build / load the pre-pass kernel specialised for this aligner and read length on this
         backend's device.  True: ready; False: there is none (the generic kernel serves the calls)."""
-        with torch.cuda.device(self.device):
-            rc = self.lib.atr_aligner_prepare(h, int(max_len), int(bool(ragged)))
-        if rc not in (0, -2):                             # (ATR_ERR_UNSUPPORTED: no specialised kernel, not an error)
-            _check(self.lib, rc, "atr_aligner_prepare")
-        return rc == 0
+        try:
+            self._call("atr_aligner_prepare", h, int(max_len), int(bool(ragged)))
+        except AtroposUnsupported:                        # (no specialised kernel, not an error)
+            return False
+        return True
 
     def locate_ascii_planes_batch(self, h, ascii_2d, lens, max_len, planes=None):
         """atr_locate_ascii_planes_batch: a long batch of ASCII rows -> (records int16 [n, 8], the packed plane64 buffer the
@@ -626,25 +991,18 @@ class HipBackend(object):
         if planes is None:
             planes = self.empty((max(self.packed_bytes(nreads, max_len), 16),), torch.uint8)
         if nreads:
-            need = self.lib.atr_locate_work_bytes(nreads)
-            if self._work is None or self._work.numel() < need:
-                self._work = self.empty((need,), torch.uint8)
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_locate_ascii_planes_batch(h, _ptr(ascii_2d), ascii_2d.stride(0), _ptr(lens), nreads,
-                                                                        int(max_len), _ptr(planes), _ptr(out), _ptr(self._work),
-                                                                        self._stream()), "atr_locate_ascii_planes_batch")
+            work = self._workspace(self._host("atr_locate_work_bytes", nreads))
+            self._call("atr_locate_ascii_planes_batch", h, _ptr(ascii_2d), ascii_2d.stride(0), _ptr(lens), nreads, int(max_len),
+                       _ptr(planes), _ptr(out), _ptr(work))
         return out, planes
 
-    def locate_planes_batch(self, h, planes, lens, nreads, max_len):
-        """Batched locate on a plane64 batch (atr_locate_planes_batch); lens None: equal-length reads."""
-        out = self.empty((nreads, 8), torch.int16)
-        if nreads:
-            need = self.lib.atr_locate_work_bytes(nreads)
-            if self._work is None or self._work.numel() < need:
-                self._work = self.empty((need,), torch.uint8)
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_locate_planes_batch(h, _ptr(planes), _ptr(lens), nreads, max_len, _ptr(out), _ptr(self._work),
-                                                                  self._stream()), "atr_locate_planes_batch")
+    def locate_ascii_batch(self, h, ascii_2d, lens, max_len):
+        """atr_locate_ascii_batch: a short batch of ASCII rows (uint8 [n, width] on the device, row stride a multiple of
+        four) through the wavefront-per-read kernel without packing; int16 [n, 8] records."""
+        n = ascii_2d.shape[0]
+        out = self.empty((n, 8), torch.int16)
+        if n:
+            self._call("atr_locate_ascii_batch", h, _ptr(ascii_2d), ascii_2d.stride(0), _ptr(lens), n, max_len, _ptr(out))
         return out
 
     def _tls_buffer(self, name, make, fits=None):
@@ -652,7 +1010,6 @@ class HipBackend(object):
         the C side stages per thread, so two threads on one backend must not share the record they read back."""
         tls = self.__dict__.get("_tls")
         if tls is None:
-            import threading
             tls = self.__dict__.setdefault("_tls", threading.local())
         buf = getattr(tls, name, None)
         if buf is None or (fits is not None and not fits(buf)):
@@ -665,8 +1022,7 @@ class HipBackend(object):
         read: atr_locate_one (the kernel reads the read from a page-locked staging buffer and writes the record
         into one; one launch, one synchronisation, no allocation).  Returns the six numbers or None."""
         rec = self._tls_buffer("one_rec", lambda: (C.c_int16 * 8)())
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_locate_one(h, query, len(query), C.addressof(rec), self._stream()), "atr_locate_one")
+        self._call("atr_locate_one", h, query, len(query), C.addressof(rec))
         return None if rec[1] < 0 else (rec[0], rec[1], rec[2], rec[3], rec[4], rec[5])
 
     def multi_locate_one(self, ref, query, e, flags, min_overlap, max_matches):
@@ -674,89 +1030,35 @@ class HipBackend(object):
         cap = max_matches + len(ref) + 2              # the last-column scan appends past max_matches (_align.pyx:750-763)
         buf = self._tls_buffer("multi_buf", lambda: (C.c_int16 * (cap * 8))(), lambda b: len(b) >= cap * 8)
         cnt = self._tls_buffer("multi_cnt", C.c_int32)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_multi_locate_one(ref, len(ref), query, len(query), e, flags, min_overlap, max_matches,
-                                                           C.addressof(buf), cap, C.addressof(cnt), self._stream()),
-                   "atr_multi_locate_one")
+        self._call("atr_multi_locate_one", ref, len(ref), query, len(query), e, flags, min_overlap, max_matches,
+                   C.addressof(buf), cap, C.addressof(cnt))
         c = cnt.value
         return None if c == 0 else [tuple(buf[8 * t:8 * t + 6]) for t in range(c)]
 
     def compare_one(self, ref, query, wildcard_ref, wildcard_query, suffix):
         """compare_prefixes / compare_suffixes of one pair of byte strings (atr_compare_one); the 6-tuple."""
         rec = self._tls_buffer("cmp_rec", lambda: (C.c_int16 * 8)())
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_compare_one(ref, len(ref), query, len(query), int(wildcard_ref), int(wildcard_query),
-                                                      int(suffix), C.addressof(rec), self._stream()), "atr_compare_one")
+        self._call("atr_compare_one", ref, len(ref), query, len(query), int(wildcard_ref), int(wildcard_query), int(suffix),
+                   C.addressof(rec))
         return (rec[0], rec[1], rec[2], rec[3], rec[4], rec[5])
 
     def locate_pair_one(self, ref_codes, revcomp_ref, query_codes, e, flags, wildcard_ref, wildcard_query, min_overlap,
                         indel_cost):
         """``Aligner(ref, ...).locate(query)`` for ONE pair of translated byte strings (atr_locate_pair_one)."""
         rec = self._tls_buffer("pair_rec", lambda: (C.c_int16 * 8)())
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_locate_pair_one(ref_codes, len(ref_codes), int(revcomp_ref), query_codes,
-                                                          len(query_codes), e, flags, int(wildcard_ref), int(wildcard_query),
-                                                          min_overlap, indel_cost, C.addressof(rec), self._stream()),
-                   "atr_locate_pair_one")
+        self._call("atr_locate_pair_one", ref_codes, len(ref_codes), int(revcomp_ref), query_codes, len(query_codes), e, flags,
+                   int(wildcard_ref), int(wildcard_query), min_overlap, indel_cost, C.addressof(rec))
         return None if rec[1] < 0 else (rec[0], rec[1], rec[2], rec[3], rec[4], rec[5])
 
     def insert_match_one(self, h, seq1, seq2):
         """``InsertAligner.match_insert`` of ONE pair of byte strings (upper-case IUPAC letters only: the caller checks);
         the three records as a flat list of 24 int16 values (atr_insert_match_one)."""
         rec = self._tls_buffer("ins_rec", lambda: (C.c_int16 * 24)())
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_insert_match_one(h, seq1, len(seq1), seq2, len(seq2), C.addressof(rec), self._stream()),
-                   "atr_insert_match_one")
+        self._call("atr_insert_match_one", h, seq1, len(seq1), seq2, len(seq2), C.addressof(rec))
         return rec
 
-    def locate_ascii_batch(self, h, ascii_2d, lens, max_len):
-        """atr_locate_ascii_batch: a short batch of ASCII rows (uint8 [n, width] on the device, row stride a multiple of
-        four) through the wavefront-per-read kernel without packing; int16 [n, 8] records."""
-        n = ascii_2d.shape[0]
-        out = self.empty((n, 8), torch.int16)
-        if n:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_locate_ascii_batch(h, _ptr(ascii_2d), ascii_2d.stride(0), _ptr(lens), n, max_len,
-                                                                 _ptr(out), self._stream()), "atr_locate_ascii_batch")
-        return out
-
-    def _small_work(self):
-        """Scratch for the short batches that do not take the wave kernel (references of more than 64 bases never
-        use it, anchored prefixes only need it to be there)."""
-        self._work = self.empty((self.lib.atr_locate_work_bytes(WAVE_MAX_READS),), torch.uint8)
-        return self._work
-
-    # -- linked adapters (one fused pipeline for the whole set) ---------------------
-    def linked_create(self, specs):
-        """specs: list of LinkedAdapterSpec.  Returns the set handle; AtroposHipError
-        ("unsupported") when the set is outside the fused kernels' envelope."""
-        arr = (LinkedAdapterSpec * len(specs))(*specs)
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_linked_create(C.addressof(arr), len(specs), C.byref(h)), "atr_linked_create")
-        return h
-
-    def linked_destroy(self, h):
-        self.lib.atr_linked_destroy(h)
-
-    def linked_match_batch(self, h, packed, lens, nreads, max_len):
-        """(which int8 [n, 2] = (first matching adapter | -1, number of matching 5' parts),
-        front int16 [n, 8], back int16 [n, 8]) -- include/atropos_hip.h, atr_linked_match_batch."""
-        which = self.empty((nreads, 2), torch.int8)
-        front = self.empty((nreads, 8), torch.int16)
-        back = self.empty((nreads, 8), torch.int16)
-        if nreads:
-            need = self.lib.atr_linked_work_bytes(h, nreads)
-            if self._work is None or self._work.numel() < need:
-                self._work = self.empty((need,), torch.uint8)
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_linked_match_batch(h, _ptr(packed), _ptr(lens), nreads, max_len, _ptr(which),
-                                                                 _ptr(front), _ptr(back), _ptr(self._work), self._stream()),
-                       "atr_linked_match_batch")
-        return which, front, back
-
     def linked_group_applies(self, h, max_len):
-        return bool(self.lib.atr_linked_group_applies(h, int(max_len)))
+        return bool(self._host("atr_linked_group_applies", h, int(max_len)))
 
     def linked_group_pack(self, h, ascii_2d, lens, max_len, table):
         """atr_linked_group_pack: the 5' parts decided from the ASCII rows, read[front.rstop:] packed as bit planes into
@@ -764,20 +1066,18 @@ class HipBackend(object):
         nreads = ascii_2d.shape[0]
         g = LinkedGroups()
         g.nreads, g.max_len = nreads, int(max_len)
-        g.grouped = self.empty((max(self.lib.atr_linked_group_bytes(nreads, max_len), 16),), torch.uint8)
+        g.grouped = self.empty((max(self._host("atr_linked_group_bytes", nreads, max_len), 16),), torch.uint8)
         g.glens = self.empty((nreads + 64 * LINKED_MAX_ADAPTERS,), torch.int32)
         g.perm = self.empty((nreads + 64 * LINKED_MAX_ADAPTERS,), torch.int32)
         g.slot_of = self.empty((nreads,), torch.int32)
         g.which = self.empty((nreads, 2), torch.int8)
         g.front = self.empty((nreads, 8), torch.int16)
         g.info = (C.c_int64 * 8)()
-        g.work = self.empty((max(self.lib.atr_linked_group_work_bytes(h, nreads), 16),), torch.uint8)
+        g.work = self.empty((max(self._host("atr_linked_group_work_bytes", h, nreads), 16),), torch.uint8)
         if nreads:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_linked_group_pack(h, _ptr(ascii_2d), ascii_2d.stride(0), _ptr(lens), nreads, int(max_len),
-                                                                table, _ptr(g.grouped), _ptr(g.glens), _ptr(g.perm), _ptr(g.slot_of),
-                                                                _ptr(g.which), _ptr(g.front), g.info, _ptr(g.work), self._stream()),
-                       "atr_linked_group_pack")
+            self._call("atr_linked_group_pack", h, _ptr(ascii_2d), ascii_2d.stride(0), _ptr(lens), nreads, int(max_len), table,
+                       _ptr(g.grouped), _ptr(g.glens), _ptr(g.perm), _ptr(g.slot_of), _ptr(g.which), _ptr(g.front), g.info,
+                       _ptr(g.work))
         return g
 
     def linked_group_match(self, h, g, ordered=True):
@@ -787,400 +1087,28 @@ class HipBackend(object):
         slab = self.empty((slots, 8), torch.int16)
         back = self.empty((g.nreads, 8), torch.int16) if ordered else None
         if g.nreads:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_linked_group_match(h, _ptr(g.grouped), _ptr(g.glens), g.info, g.max_len, _ptr(g.slot_of),
-                                                                 _ptr(g.which), g.nreads, _ptr(slab), _ptr(back), _ptr(g.work),
-                                                                 self._stream()), "atr_linked_group_match")
+            self._call("atr_linked_group_match", h, _ptr(g.grouped), _ptr(g.glens), g.info, g.max_len, _ptr(g.slot_of),
+                       _ptr(g.which), g.nreads, _ptr(slab), _ptr(back), _ptr(g.work))
         return slab, back
-
-    def locate_debug(self, h, packed, m, n):
-        """atr_locate_debug: (cost matrix int32 [m + 1, n + 1] on the host, INT32_MIN = not computed; the record)."""
-        work = self.empty((max(self.lib.atr_locate_debug_bytes(h, n), 16),), torch.uint8)
-        out = self.empty((1, 8), torch.int16)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_locate_debug(h, _ptr(packed), n, _ptr(work), _ptr(out), self._stream()),
-                   "atr_locate_debug")
-        cells = (m + 1) * (n + 1)
-        return work[:4 * cells].view(torch.int32).reshape(m + 1, n + 1).cpu(), out.cpu()
-
-    def compare_packed(self, h, packed, lens, nreads, max_len, suffix):
-        """atr_compare_packed: compare_prefixes / compare_suffixes of aligner ``h``'s reference against
-        reads packed for it.  int16 [nreads, 8]."""
-        out = self.empty((nreads, 8), torch.int16)
-        if nreads:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_compare_packed(h, _ptr(packed), _ptr(lens), nreads, max_len, int(suffix),
-                                                             _ptr(out), self._stream()), "atr_compare_packed")
-        return out
-
-    def locate_pairs_batch(self, ref_packed, ref_lens, ref_max_len, revcomp_ref, query_packed, query_lens,
-                           query_max_len, npairs, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost,
-                           need=None, path="auto"):
-        """Aligner.locate with a per-pair reference; both sides tile64-packed.  int16 [npairs, 8].
-        need: int32 [npairs] or None -- alignments with fewer matches may come back as None
-        (atr_locate_pairs_need_batch).  path: PAIRS_PATHS ("auto": a wavefront per pair for short batches, the
-        cost / threat / band pipeline or the full sweep for long ones; "full", "fast", "wave": that family)."""
-        out = self.empty((npairs, 8), torch.int16)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_locate_pairs_path_batch(
-                _ptr(ref_packed), _ptr(ref_lens), ref_max_len, int(revcomp_ref), _ptr(query_packed), _ptr(query_lens),
-                query_max_len, npairs, e, flags, int(wildcard_ref), int(wildcard_query), min_overlap, indel_cost,
-                _ptr(need), PAIRS_PATHS[path], _ptr(out), self._stream()), "atr_locate_pairs_path_batch")
-        return out
-
-    def locate_pairs_long_batch(self, ref_packed, ref_lens, ref_max_len, revcomp_ref, query_packed, query_lens,
-                                query_max_len, npairs, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost):
-        """Pairs with a side beyond PAIRS_MAX_LEN (atr_locate_pairs_long_batch: 64-bit cells, the DP column in a
-        workspace allocated here).  The caller keeps npairs * ref_max_len small (PairAligner chunks)."""
-        out = self.empty((npairs, 8), torch.int16)
-        if npairs:
-            work = self.empty((max(self.lib.atr_locate_pairs_long_work_bytes(npairs, ref_max_len), 16),), torch.uint8)
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_locate_pairs_long_batch(
-                    _ptr(ref_packed), _ptr(ref_lens), ref_max_len, int(revcomp_ref), _ptr(query_packed), _ptr(query_lens),
-                    query_max_len, npairs, e, flags, int(wildcard_ref), int(wildcard_query), min_overlap, indel_cost,
-                    _ptr(out), _ptr(work), self._stream()), "atr_locate_pairs_long_batch")
-        return out
-
-    def locate_pairs_full_batch(self, ref_packed, ref_lens, ref_max_len, revcomp_ref, query_packed, query_lens,
-                                query_max_len, npairs, e, flags, min_overlap, indel_cost):
-        """The same records by the full-matrix sweep alone (atr_locate_pairs_full_batch)."""
-        out = self.empty((npairs, 8), torch.int16)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_locate_pairs_full_batch(
-                _ptr(ref_packed), _ptr(ref_lens), ref_max_len, int(revcomp_ref), _ptr(query_packed), _ptr(query_lens),
-                query_max_len, npairs, e, flags, 0, 0, min_overlap, indel_cost, _ptr(out), self._stream()),
-                "atr_locate_pairs_full_batch")
-        return out
-
-    # -- device-resident FASTQ batch --------------------------------------------
-    def fastq_index(self, data, nbytes):
-        """data: uint8 device tensor holding nbytes of FASTQ text (16-byte aligned, readable up
-        to the next multiple of 16).  Returns (records uint32 [nrec, 8], nlines, error word)."""
-        work = self.empty((max(self.lib.atr_fastq_work_bytes(nbytes), 16),), torch.uint8)
-        info = self.empty((2,), torch.int64)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_fastq_count_lines(_ptr(data), nbytes, _ptr(work), _ptr(info), self._stream()),
-                   "atr_fastq_count_lines")
-            nlines = int(info[0].item())
-            line_ends = self.empty((max(nlines, 1),), torch.int32)
-            records = self.empty((nlines // 4, 8), torch.int32)
-            _check(self.lib, self.lib.atr_fastq_index(_ptr(data), nbytes, _ptr(work), _ptr(line_ends), nlines,
-                                                      _ptr(records), C.c_void_p(info.data_ptr() + 8), self._stream()),
-                   "atr_fastq_index")
-            err = int(info[1].item())
-        return records, line_ends, nlines, err
-
-    def pack_records(self, data, records, begin, end, max_len, table, count_invalid=False, planes=False):
-        n = records.shape[0]
-        packed = self.empty((max(self.packed_bytes(n, max_len), 16),), torch.uint8)
-        lens = self.empty((n,), torch.int32)
-        invalid = torch.zeros((1,), dtype=torch.int32, device=self.device) if count_invalid else None
-        if n:
-            with torch.cuda.device(self.device):
-                _check(self.lib, self.lib.atr_pack_records(_ptr(data), _ptr(records), _ptr(begin), _ptr(end), n, max_len,
-                                                           table, int(planes), _ptr(packed), _ptr(lens), _ptr(invalid),
-                                                           self._stream()), "atr_pack_records")
-        return (packed, lens, int(invalid.item())) if count_invalid else (packed, lens)
-
-    def clip_batch(self, records, begin, end, front, back):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_clip_batch(_ptr(records), _ptr(begin), _ptr(end), begin.shape[0], front, back,
-                                                     self._stream()), "atr_clip_batch")
-
-    def quality_trim_batch(self, data, records, begin, end, cutoff_front, cutoff_back, base, nextseq):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_quality_trim_batch(_ptr(data), _ptr(records), _ptr(begin), _ptr(end),
-                                                             begin.shape[0], cutoff_front, cutoff_back, base,
-                                                             int(nextseq), self._stream()), "atr_quality_trim_batch")
-
-    def nend_trim_batch(self, data, records, begin, end, ubegin=None, uend=None):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_nend_trim_batch(_ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin),
-                                                          _ptr(uend), begin.shape[0], self._stream()),
-                   "atr_nend_trim_batch")
-
-    def match_trim_batch(self, matches, front, default_front, begin, end, active, matched):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_match_trim_batch(_ptr(matches), _ptr(front), default_front, _ptr(begin),
-                                                           _ptr(end), _ptr(active), _ptr(matched), begin.shape[0],
-                                                           self._stream()), "atr_match_trim_batch")
-
-    def read_filter_batch(self, data, records, begin, end, ubegin, uend, matched, min_len, max_len, max_n,
-                          discard_trimmed, discard_untrimmed, masks=False):
-        """The destination byte per read, or (masks=True) the bit mask of the filters that fire."""
-        out = self.empty((begin.shape[0],), torch.uint8)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_read_filter_batch(
-                _ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(matched),
-                begin.shape[0], min_len, max_len, max_n, int(discard_trimmed), int(discard_untrimmed),
-                None if masks else _ptr(out), _ptr(out) if masks else None, self._stream()), "atr_read_filter_batch")
-        return out
-
-    def pair_filter_batch(self, mask1, mask2, min_affected):
-        dest = self.empty((mask1.shape[0],), torch.uint8)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_pair_filter_batch(_ptr(mask1), _ptr(mask2), mask1.shape[0], min_affected,
-                                                            _ptr(dest), self._stream()), "atr_pair_filter_batch")
-        return dest
-
-    def insert_plan_batch(self, insert, fb1, fb2, batch1, batch2, begin1, end1, begin2, end2, uend1, uend2,
-                          min_insert_len, symmetric, trim_action, correct_action=-1, min_qual_difference=1, comp=None):
-        """InsertAdapterCutter's decision logic (+ optional in-place error correction of the two
-        FASTQ chunks).  Returns (matched1, matched2, corrected int32 [n, 2], error word)."""
-        n = begin1.shape[0]
-        m1, m2 = self.empty((n,), torch.uint8), self.empty((n,), torch.uint8)
-        corrected = self.empty((n, 2), torch.int32)
-        err = self.empty((1,), torch.int64)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_insert_plan_batch(
-                _ptr(insert), _ptr(fb1), _ptr(fb2), _ptr(batch1.data), _ptr(batch1.records), _ptr(batch2.data),
-                _ptr(batch2.records), _ptr(begin1), _ptr(end1), _ptr(begin2), _ptr(end2), _ptr(uend1), _ptr(uend2), n,
-                min_insert_len, int(symmetric), trim_action, correct_action, min_qual_difference, comp, _ptr(m1),
-                _ptr(m2), _ptr(corrected), _ptr(err), self._stream()), "atr_insert_plan_batch")
-        return m1, m2, corrected, int(err.item())
-
-    def merge_batch(self, align, need, insert_matched, batch1, batch2, begin1, end1, begin2, end2, correct_action=-1,
-                    min_qual_difference=1, comp=None):
-        """MergeOverlapping after the alignments (atr_merge_plan_batch + atr_merge_emit_batch): returns
-        (kind uint8 [n] -- 0: the pair stays a pair --, the FASTQ text of the merged reads in input order,
-        corrected int32 [n, 2], error word).  With a mismatch action the two chunks are corrected in place."""
-        n = begin1.shape[0]
-        kind = self.empty((n,), torch.uint8)
-        offsets = self.empty((n + 1,), torch.int64)
-        corrected = self.empty((n, 2), torch.int32)
-        corrected.zero_()
-        err = self.empty((1,), torch.int64)
-        work = self.empty((max(self.lib.atr_merge_work_bytes(n), 16),), torch.uint8)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_merge_plan_batch(
-                _ptr(align), _ptr(need), _ptr(batch1.records), _ptr(begin1), _ptr(end1), _ptr(begin2), _ptr(end2), n,
-                _ptr(kind), _ptr(offsets), _ptr(work), _ptr(err), self._stream()), "atr_merge_plan_batch")
-            total = int(offsets[n].item())
-            out = self.empty((max(total, 1),), torch.uint8)
-            if total and int(err.item()) == INT64_MAX:
-                _check(self.lib, self.lib.atr_merge_emit_batch(
-                    _ptr(align), _ptr(kind), _ptr(insert_matched), _ptr(batch1.data), _ptr(batch1.records),
-                    _ptr(batch2.data), _ptr(batch2.records), _ptr(begin1), _ptr(end1), _ptr(begin2), _ptr(end2), n,
-                    correct_action, min_qual_difference, comp, _ptr(offsets), _ptr(corrected), _ptr(err), _ptr(out),
-                    self._stream()), "atr_merge_emit_batch")
-        return kind, out[:total], corrected, int(err.item())
-
-    def fastq_emit(self, data, records, begin, end, ubegin, uend, dest, which):
-        """Formatted FASTQ text (uint8 device tensor) of the records with dest == which."""
-        n = records.shape[0]
-        offsets = self.empty((n + 1,), torch.int64)
-        work = self.empty((max(self.lib.atr_fastq_emit_work_bytes(n), 16),), torch.uint8)
-        with torch.cuda.device(self.device):
-            hint = int(data.numel() // max(n, 1))
-            args = (_ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(dest), which, n,
-                    hint, _ptr(offsets), _ptr(work))
-            _check(self.lib, self.lib.atr_fastq_emit(*args, None, self._stream()), "atr_fastq_emit")
-            total = int(offsets[n].item())
-            out = self.empty((max(total, 1),), torch.uint8)
-            if total:
-                _check(self.lib, self.lib.atr_fastq_emit(*args, _ptr(out), self._stream()), "atr_fastq_emit")
-        return out[:total]
-
-    def fastq_emit_grouped(self, data, records, begin, end, ubegin, uend, group, n_groups):
-        """atr_fastq_emit for ``n_groups`` outputs in one pass: (text, bounds) -- the formatted records with
-        ``group[r]`` (int32) == 0 first, then those of group 1 ..., input order inside a group, as one uint8 device
-        tensor, and the ``n_groups + 1`` segment boundaries as a list of ints.  Records with any other code are not
-        written."""
-        n = records.shape[0]
-        n_groups = int(n_groups)
-        if n_groups > EMIT_MAX_GROUPS:
-            raise AtroposUnsupported("atr_fastq_emit_grouped: %d outputs (at most %d)" % (n_groups, EMIT_MAX_GROUPS))
-        offsets = self.empty((max(n, 1),), torch.int64)
-        bounds = self.empty((max(n_groups, 0) + 1,), torch.int64)
-        work = self.empty((max(self.lib.atr_fastq_emit_grouped_work_bytes(n, n_groups), 16),), torch.uint8)
-        with torch.cuda.device(self.device):
-            hint = int(data.numel() // max(n, 1))
-            args = (_ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(group), n_groups, n,
-                    hint, _ptr(offsets), _ptr(bounds), _ptr(work))
-            _check(self.lib, self.lib.atr_fastq_emit_grouped(*args, None, self._stream()), "atr_fastq_emit_grouped")
-            edges = bounds.cpu().tolist()
-            out = self.empty((max(edges[-1], 1),), torch.uint8)
-            if edges[-1]:
-                _check(self.lib, self.lib.atr_fastq_emit_grouped(*args, _ptr(out), self._stream()), "atr_fastq_emit_grouped")
-        return out[:edges[-1]], edges
-
-    def demux_groups(self, dest, matched, last_which, adapter_group, n_adapters, untrimmed_group):
-        """The output code of every read of a demultiplexed run (atr_demux_groups): int32 device tensor."""
-        n = dest.shape[0]
-        group = self.empty((n,), torch.int32)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_demux_groups(_ptr(dest), _ptr(matched), _ptr(last_which), _ptr(adapter_group),
-                                                       int(n_adapters), int(untrimmed_group), n, _ptr(group), self._stream()),
-                   "atr_demux_groups")
-        return group
-
-    # -- .gz output on the device (atr_gzip_*) ------------------------------------------------------------------
-    def gzip_bound(self, nbytes):
-        return _check(self.lib, self.lib.atr_gzip_bound(int(nbytes)), "atr_gzip_bound")
-
-    def gzip_blocks(self, text, offsets=False):
-        """``text`` (uint8 device tensor) as a stream of BGZF members, one per ``GZIP_BLOCK`` bytes: (stream, total) --
-        a uint8 device tensor whose first ``total`` bytes are the members in input order -- and with ``offsets`` also
-        the int64 device tensor of the member starts followed by the total.  Reading ``total`` waits for the kernels."""
-        n = int(text.numel())
-        if not text.is_contiguous():
-            text = text.contiguous()
-        cap = self.gzip_bound(n)
-        out = self.empty((max(cap, 1),), torch.uint8)
-        total = self.empty((1,), torch.int64)
-        starts = self.empty(((n + GZIP_BLOCK - 1) // GZIP_BLOCK + 1,), torch.int64) if offsets else None
-        work = self.empty((max(self.lib.atr_gzip_work_bytes(n), 16),), torch.uint8)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_gzip_blocks(_ptr(text), n, _ptr(out), cap, _ptr(total), _ptr(starts), _ptr(work),
-                                                      self._stream()), "atr_gzip_blocks")
-            size = int(total.item())
-        return (out, size, starts) if offsets else (out, size)
-
-    # -- BGZF .gz input on the device (atr_bgzf_scan, atr_gunzip_members) ------------------------------------------
-    def bgzf_scan(self, buf, lo, hi, max_members):
-        """The whole BGZF members at the front of ``buf[lo:hi]`` (a uint8 HOST tensor), at most ``max_members``:
-        (member_at, text_at, k, covered, ok) -- int64 host tensors whose entries 0 .. k are the members' offsets from
-        ``lo`` and the running sum of their text sizes; ``covered`` = member_at[k]; ``ok`` is False when the walk
-        stopped at a header that is no BGZF member (at ``lo + covered``)."""
-        return _bgzf_scan(self.lib.atr_bgzf_scan, buf, lo, hi, max_members)
-
-    def gunzip_members(self, stream, n_stream, member_at, text_at, n_members, text, capacity):
-        """Inflate ``n_members`` BGZF members of ``stream`` (uint8 device tensor, readable to the next multiple of 16
-        beyond ``n_stream``) into ``text[text_at[m]:text_at[m + 1]]``; ``member_at`` / ``text_at``: int64 device
-        tensors.  Returns (status int32 [n_members], bad int32 [1]) on the device: nothing here waits for the kernel."""
-        status = self.empty((max(int(n_members), 1),), torch.int32)
-        bad = self.empty((1,), torch.int32)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_gunzip_members(_ptr(stream), int(n_stream), _ptr(member_at), _ptr(text_at), int(n_members),
-                                                         _ptr(text), int(capacity), _ptr(status), _ptr(bad), self._stream()),
-                   "atr_gunzip_members")
-        return status, bad
 
     # -- read statistics (atr_read_stats_*) ---------------------------------------------------------------------
     def read_stats_words(self, max_len):
         """uint64 words of a statistics block for reads of up to ``max_len`` bases."""
-        return _check(self.lib, self.lib.atr_read_stats_bytes(int(max_len)), "atr_read_stats_bytes") // 8
+        return self._host("atr_read_stats_bytes", int(max_len)) // 8
 
     def read_stats_clear(self, block, max_len):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_read_stats_clear(_ptr(block), int(max_len), self._stream()),
-                   "atr_read_stats_clear")
+        self._call("atr_read_stats_clear", _ptr(block), int(max_len))
 
     def read_stats_batch(self, block, max_len, longest, quality_base, data, records, begin=None, end=None, ubegin=None,
                          uend=None, dest=None, which=0, index_base=0):
         """Adds the records (their kept intervals, masks and destination filter as atr_fastq_emit) into ``block``;
         record r is read ``index_base + r`` of the stream."""
-        n = records.shape[0]
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_read_stats_batch(
-                _ptr(block), int(max_len), int(longest), int(quality_base), _ptr(data), _ptr(records), _ptr(begin),
-                _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(dest), int(which), n, int(index_base), self._stream()),
-                "atr_read_stats_batch")
+        self._call("atr_read_stats_batch", _ptr(block), int(max_len), int(longest), int(quality_base), _ptr(data),
+                   _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(dest), int(which), records.shape[0],
+                   int(index_base))
 
     def read_stats_merge(self, dst, dst_max_len, src, src_max_len, index_offset=0):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_read_stats_merge(_ptr(dst), int(dst_max_len), _ptr(src), int(src_max_len),
-                                                           int(index_offset), self._stream()), "atr_read_stats_merge")
-
-    # -- known-contaminant detection (atr_detect_*) ---------------------------------------------------------------
-    def detect_create(self, seqs, kmer_size, past_end_bases, thresholds, complexity, max_len):
-        """seqs: list of bytes; thresholds: list of int (-1 = never); complexity: float64 ndarray
-        [max_len + 1, max_len + 1].  Returns the handle."""
-        lens = np.asarray([len(s) for s in seqs], dtype=np.int32)
-        thr = np.asarray(thresholds, dtype=np.int32)
-        cx = np.ascontiguousarray(complexity, dtype=np.float64)
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_detect_create(b"".join(seqs), lens.ctypes.data, len(seqs), int(kmer_size),
-                                                        bytes(past_end_bases), len(past_end_bases), thr.ctypes.data,
-                                                        cx.ctypes.data, int(max_len), C.byref(h)), "atr_detect_create")
-        return h
-
-    def detect_destroy(self, h):
-        self.lib.atr_detect_destroy(h)
-
-    def detect_counters(self, h):
-        """A zeroed counter block (int64 tensor; the words are uint64 counters)."""
-        words = _check(self.lib, self.lib.atr_detect_counter_bytes(h), "atr_detect_counter_bytes") // 8
-        block = self.empty((words,), torch.int64)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_detect_clear(h, _ptr(block), self._stream()), "atr_detect_clear")
-        return block
-
-    def detect_filter(self, h, data, records, longest, counters):
-        """(kept int32 [n], hashes int64 [n]) of the records."""
-        n = records.shape[0]
-        kept = self.empty((n,), torch.int32)
-        hashes = self.empty((n,), torch.int64)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_detect_filter_batch(h, _ptr(data), _ptr(records), n, int(longest), _ptr(kept),
-                                                              _ptr(hashes), _ptr(counters), self._stream()),
-                   "atr_detect_filter_batch")
-        return kept, hashes
-
-    def detect_mark(self, h, data, records, kept, order, head, counters):
-        """rep uint8 [m]: 1 for one read of every distinct kept sequence (order / head: int64 [m])."""
-        m = order.shape[0]
-        rep = self.empty((m,), torch.uint8)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_detect_mark_batch(h, _ptr(data), _ptr(records), _ptr(kept), _ptr(order), _ptr(head),
-                                                            m, _ptr(rep), _ptr(counters), self._stream()),
-                   "atr_detect_mark_batch")
-        return rep
-
-    def detect_match(self, h, data, records, kept, order, rep, counters):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_detect_batch(h, _ptr(data), _ptr(records), _ptr(kept), _ptr(order), _ptr(rep),
-                                                       order.shape[0], _ptr(counters), self._stream()), "atr_detect_batch")
-
-    def detect_read(self, h, counters):
-        """The counter block as a host int64 ndarray."""
-        out = np.zeros((counters.shape[0],), dtype=np.int64)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_detect_read(h, _ptr(counters), out.ctypes.data, self._stream()), "atr_detect_read")
-        return out
-
-    # -- the trim report (atr_report_*) ---------------------------------------------------------------------------
-    def report_create(self, n_adapters, max_read_len, max_errors):
-        h = C.c_void_p()
-        _check(self.lib, self.lib.atr_report_create(int(n_adapters), int(max_read_len), int(max_errors), C.byref(h)),
-               "atr_report_create")
-        return h
-
-    def report_destroy(self, h):
-        self.lib.atr_report_destroy(h)
-
-    def report_counters(self, h):
-        """A zeroed counter block (int64 tensor) for the handle's layout."""
-        words = _check(self.lib, self.lib.atr_report_counters(h), "atr_report_counters")
-        return torch.zeros((words,), dtype=torch.int64, device=self.device)
-
-    def report_intervals(self, h, records, begin0, end0, begin1, end1, mode, front, back, slot, counters):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_report_intervals(h, _ptr(records), _ptr(begin0), _ptr(end0), _ptr(begin1), _ptr(end1),
-                                                           begin0.shape[0], int(mode), int(front), int(back), int(slot),
-                                                           _ptr(counters), self._stream()), "atr_report_intervals")
-
-    def report_adapters(self, h, data, records, took, best, which, front, default_front, begin, end, longest, weight,
-                        variant, counters):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_report_adapters(h, _ptr(data), _ptr(records), _ptr(took), _ptr(best), _ptr(which),
-                                                          _ptr(front), int(default_front), _ptr(begin), _ptr(end),
-                                                          begin.shape[0], int(longest), int(weight), int(variant),
-                                                          _ptr(counters), self._stream()), "atr_report_adapters")
-
-    def report_outputs(self, h, records, begin, end, matched, dest, counters):
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_report_outputs(h, _ptr(records), _ptr(begin), _ptr(end), _ptr(matched), _ptr(dest),
-                                                         begin.shape[0], _ptr(counters), self._stream()), "atr_report_outputs")
-
-    def report_read(self, h, counters):
-        """The counter block as a host int64 ndarray (the one device -> host copy of a report)."""
-        out = np.zeros((counters.shape[0],), dtype=np.int64)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.atr_report_read(h, _ptr(counters), out.ctypes.data, self._stream()), "atr_report_read")
-        return out
+        self._call("atr_read_stats_merge", _ptr(dst), int(dst_max_len), _ptr(src), int(src_max_len), int(index_offset))
 
 
 _backend = None

@@ -276,19 +276,11 @@ def emit_call(be, data, recs, begin, end, ubegin, uend, dest, which, hint, out_m
     n = recs.shape[0]
     ptr = _lib._ptr
     offsets = torch.zeros((n + 1,), dtype=torch.int64, device=be.device)
-    if be.name == "hip":
-        work = be.empty((max(be.lib.atr_fastq_emit_work_bytes(n), 16),), torch.uint8)
+    work = be.empty((max(be._host("atr_fastq_emit_work_bytes", n), 16),), torch.uint8)
 
-        def call(out_ptr):
-            with torch.cuda.device(be.device):
-                _lib._check(be.lib, be.lib.atr_fastq_emit(ptr(data), ptr(recs), ptr(begin), ptr(end), ptr(ubegin), ptr(uend),
-                                                           ptr(dest), which, n, hint, ptr(offsets), ptr(work), out_ptr,
-                                                           be._stream()), "atr_fastq_emit")
-    else:
-        def call(out_ptr):
-            rc = be.lib.emu_fastq_emit(ptr(data), ptr(recs), ptr(begin), ptr(end), ptr(ubegin), ptr(uend), ptr(dest), which,
-                                       C.c_int64(n), ptr(offsets), out_ptr)
-            assert rc == 0
+    def call(out_ptr):
+        be._call("atr_fastq_emit", ptr(data), ptr(recs), ptr(begin), ptr(end), ptr(ubegin), ptr(uend), ptr(dest), which, n, hint,
+                 ptr(offsets), ptr(work), out_ptr)
     call(None)
     _sync(be)
     offs = offsets.cpu().tolist()

@@ -3,7 +3,6 @@ writer, the block walker, the member cases, the corrupt corpus and the checks of
 ``gunzip_members``, ``device_gunzip=True``).  The oracle for text is ``zlib.decompress(member, 31)`` /
 ``gzip.decompress``; the members come from ``zlib.compressobj`` (raw deflate, framed here) and from the project's own
 compressor.  Nothing here includes or calls the inflater under test except through a backend."""
-import ctypes as C
 import functools
 import gzip
 import os
@@ -14,61 +13,24 @@ import zlib
 import numpy as np
 import torch
 
-from atropos_amd import _lib
-
 from . import _deflate_ref as R
 from . import _gzip_common as G
 from .conftest import ROOT
-from .emu.backend import _check, _ptr
+from .emu.backend import stale, twin_sources
 
 FILL = 0xa5
-_HERE = os.path.join(ROOT, "tests", "emu")
-_INC = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "atropos_amd", "csrc")]
-_SO = os.path.join(_HERE, "libemu_gunzip.so")
-_FUZZ = os.path.join(_HERE, "gunzip_fuzz")
-_SRCS = [os.path.join(_HERE, "emu_gunzip.cpp"), os.path.join(ROOT, "atropos_amd", "csrc", "inflate_core.hpp"),
-         os.path.join(ROOT, "atropos_amd", "csrc", "deflate_core.hpp"), os.path.join(ROOT, "include", "atropos_hip.h")]
-
-
-def _stale(out, srcs):
-    return not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs)
-
-
-def build_twin():
-    if _stale(_SO, _SRCS):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DATR_HOST_EMU"] + _INC + [_SRCS[0], "-o", _SO])
-    return _SO
 
 
 def build_fuzz():
     """The stand-alone sanitized program (its own ``main``): address and undefined-behaviour sanitizers over the twin."""
-    main = os.path.join(_HERE, "gunzip_fuzz_main.cpp")
-    if _stale(_FUZZ, _SRCS + [main]):
+    main = os.path.join(ROOT, "tests", "emu", "gunzip_fuzz_main.cpp")
+    prog = os.path.join(ROOT, "tests", "emu", "gunzip_fuzz")
+    cpps, deps = twin_sources("gunzip")
+    if stale(prog, deps + [main]):
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                               "-static-libasan", "-static-libubsan", "-DATR_HOST_EMU"] + _INC + [main, _SRCS[0], "-o", _FUZZ])
-    return _FUZZ
-
-
-class GunzipEmuBackend(G.GzipEmuBackend):
-    """The CPU test backend plus the twins of the device gzip compressor and of the device gunzip."""
-
-    def __init__(self):
-        super().__init__()
-        self.gunz = C.CDLL(build_twin())
-        self.gunz.emu_gunzip_members.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                 C.c_void_p, C.c_void_p]
-        self.inflate_calls = 0
-
-    def bgzf_scan(self, buf, lo, hi, max_members):
-        return _lib._bgzf_scan(self.gunz.emu_bgzf_scan, buf, lo, hi, max_members)
-
-    def gunzip_members(self, stream, n_stream, member_at, text_at, n_members, text, capacity):
-        self.inflate_calls += 1
-        status = torch.zeros((max(int(n_members), 1),), dtype=torch.int32)
-        bad = torch.zeros((1,), dtype=torch.int32)
-        _check(self.gunz.emu_gunzip_members(_ptr(stream), int(n_stream), _ptr(member_at), _ptr(text_at), int(n_members), _ptr(text),
-                                            int(capacity), _ptr(status), _ptr(bad)), "emu_gunzip_members")
-        return status, bad
+                               "-static-libasan", "-static-libubsan", "-DATR_HOST_EMU", "-I" + os.path.join(ROOT, "include"),
+                               "-I" + os.path.join(ROOT, "atropos_amd", "csrc"), main] + cpps + ["-o", prog])
+    return prog
 
 
 # ---------------------------------------------------------------------------------------------- the BGZF writer

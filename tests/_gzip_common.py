@@ -5,9 +5,7 @@ import ctypes as C
 import functools
 import gzip
 import heapq
-import os
 import struct
-import subprocess
 import zlib
 
 import numpy as np
@@ -16,8 +14,7 @@ import torch
 from atropos_amd import synth
 
 from . import _deflate_ref as R
-from .conftest import ROOT
-from .emu.backend import EmuBackend, _check, _ptr
+from .emu.backend import load_twin
 
 BLOCK = 65280
 EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
@@ -29,64 +26,16 @@ EDGE_LENGTHS = (127, 128, 129, 511, 512, 513, 1023, 1024, 1025, 16383, 16384, 16
 EDGE_CONTENTS = ("synth_fastq", "one_byte", "fibonacci", "every_symbol")
 TRUSEQ = "AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
 
-_HERE = os.path.join(ROOT, "tests", "emu")
-_SO = os.path.join(_HERE, "libemu_gzip.so")
-_SRCS = [os.path.join(_HERE, "emu_gzip.cpp"), os.path.join(ROOT, "atropos_amd", "csrc", "deflate_core.hpp"),
-         os.path.join(ROOT, "include", "atropos_hip.h")]
-
-
-def build_twin():
-    if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DATR_HOST_EMU",
-                               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "atropos_amd", "csrc"),
-                               _SRCS[0], "-o", _SO])
-    return _SO
-
-
-def load_twin():
-    lib = C.CDLL(build_twin())
-    lib.emu_gzip_bound.restype = C.c_int64
-    lib.emu_gzip_bound.argtypes = [C.c_int64]
-    lib.emu_gzip_work_bytes.restype = C.c_size_t
-    lib.emu_gzip_work_bytes.argtypes = [C.c_int64]
-    lib.emu_gzip_eof.argtypes = [C.c_void_p]
-    lib.emu_gzip_blocks.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.emu_gzip_build_lengths.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    return lib
-
-
-def twin_build_lengths(lib, freqs, maxbits):
+def twin_build_lengths(freqs, maxbits):
     """``gz_build_lengths`` of the twin over ``freqs`` (ascending, nonzero): the code length of every frequency."""
+    fn = load_twin("gzip")[0].emu_gzip_build_lengths
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     key = np.asarray(freqs, dtype=np.uint32)
     out = np.zeros((len(key),), dtype=np.uint8)
     blc = np.zeros((16,), dtype=np.uint32)
-    assert lib.emu_gzip_build_lengths(key.ctypes.data, len(key), maxbits, out.ctypes.data, blc.ctypes.data) == 0
+    assert fn(key.ctypes.data, len(key), maxbits, out.ctypes.data, blc.ctypes.data) == 0
     assert [int((out == l).sum()) for l in range(1, 16)] == blc[1:].tolist()
     return out.tolist()
-
-
-class GzipEmuBackend(EmuBackend):
-    """The CPU test backend plus the twin of the device gzip compressor."""
-
-    def __init__(self):
-        super().__init__()
-        self.gz = load_twin()
-
-    def gzip_bound(self, nbytes):
-        return _check(self.gz.emu_gzip_bound(int(nbytes)), "emu_gzip_bound")
-
-    def gzip_blocks(self, text, offsets=False):
-        n = int(text.numel())
-        text = text.contiguous()
-        cap = self.gzip_bound(n)
-        out = torch.zeros((max(cap, 1),), dtype=torch.uint8)
-        total = torch.zeros((1,), dtype=torch.int64)
-        starts = torch.zeros(((n + BLOCK - 1) // BLOCK + 1,), dtype=torch.int64) if offsets else None
-        work = torch.zeros((max(self.gz.emu_gzip_work_bytes(n), 16),), dtype=torch.uint8)
-        _check(self.gz.emu_gzip_blocks(_ptr(text), C.c_int64(n), _ptr(out), C.c_int64(cap), _ptr(total), _ptr(starts),
-                                       _ptr(work)), "emu_gzip_blocks")
-        size = int(total.item())
-        return (out, size, starts) if offsets else (out, size)
 
 
 def compress(backend, data, offsets=False):

@@ -1,80 +1,16 @@
 """Shared by test_report_host.py and test_gpu_report.py: the golden cases of tests/golden/trim_report.json.gz, the
-comparison rule, the per-object host path the small shapes are compared with, and the loader of the CPU twin
-(tests/emu/emu_report.cpp)."""
+comparison rule, and the per-object host path the small shapes are compared with."""
 import base64
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
-import torch
 
-from atropos_amd import _lib
 from atropos_amd.fastq import FastqBatch
 from atropos_amd.report import TrimReport
 from atropos_amd.trim import pipeline_from_args
 
-from .conftest import ROOT, load_golden
-from .emu.backend import EmuBackend, _check, _ptr
+from .conftest import load_golden
 
-_HERE = os.path.join(ROOT, "tests", "emu")
-_SO = os.path.join(_HERE, "libemu_report.so")
-_SRCS = [os.path.join(_HERE, "emu_report.cpp"), os.path.join(ROOT, "atropos_amd", "csrc", "report_core.hpp"),
-         os.path.join(ROOT, "atropos_amd", "csrc", "fastq_core.hpp"), os.path.join(ROOT, "include", "atropos_hip.h")]
 KINDS = ("info", "rest", "wildcard", "too_short", "too_short2", "too_long", "too_long2", "untrimmed", "untrimmed2")
-
-
-def build_twin():
-    if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DATR_HOST_EMU",
-                               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "atropos_amd", "csrc"),
-                               _SRCS[0], "-o", _SO])
-    return _SO
-
-
-class ReportEmuBackend(EmuBackend):
-    """The CPU test backend plus the report twin."""
-
-    def __init__(self):
-        super().__init__()
-        self.rep = C.CDLL(build_twin())
-        self.rep.emu_report_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        self.rep.emu_report_destroy.restype = None
-        self.rep.emu_report_destroy.argtypes = [C.c_void_p]
-        self.rep.emu_report_counters.restype = C.c_int64
-        self.rep.emu_report_counters.argtypes = [C.c_void_p]
-        self.rep.emu_report_intervals.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        self.rep.emu_report_adapters.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                                                    C.c_int, C.c_int, C.c_void_p]
-        self.rep.emu_report_outputs.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]
-
-    def report_create(self, n_adapters, max_read_len, max_errors):
-        h = C.c_void_p()
-        _check(self.rep.emu_report_create(int(n_adapters), int(max_read_len), int(max_errors), C.byref(h)), "atr_report_create")
-        return h
-
-    def report_destroy(self, h):
-        self.rep.emu_report_destroy(h)
-
-    def report_counters(self, h):
-        return torch.zeros((self.rep.emu_report_counters(h),), dtype=torch.int64)
-
-    def report_intervals(self, h, records, begin0, end0, begin1, end1, mode, front, back, slot, counters):
-        _check(self.rep.emu_report_intervals(h, _ptr(records), _ptr(begin0), _ptr(end0), _ptr(begin1), _ptr(end1),
-                                             begin0.shape[0], mode, front, back, slot, _ptr(counters)), "atr_report_intervals")
-
-    def report_adapters(self, h, data, records, took, best, which, front, default_front, begin, end, longest, weight, variant,
-                        counters):
-        _check(self.rep.emu_report_adapters(h, _ptr(data), _ptr(records), _ptr(took), _ptr(best), _ptr(which), _ptr(front),
-                                            int(default_front), _ptr(begin), _ptr(end), begin.shape[0], int(longest),
-                                            int(weight), int(variant), _ptr(counters)), "atr_report_adapters")
-
-    def report_outputs(self, h, records, begin, end, matched, dest, counters):
-        _check(self.rep.emu_report_outputs(h, _ptr(records), _ptr(begin), _ptr(end), _ptr(matched), _ptr(dest),
-                                           begin.shape[0], _ptr(counters)), "atr_report_outputs")
-
-    def report_read(self, h, counters):
-        return counters.numpy().copy()
 
 
 # ---------------------------------------------------------------------------------------------- golden cases

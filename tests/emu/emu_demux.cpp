@@ -5,16 +5,19 @@
 #include <stdint.h>
 #include <vector>
 
-#include "atropos_hip.h"
+#include "emu_abi.hpp"
 #include "demux_core.hpp"
 
 using namespace atr;
 
 extern "C" {
 
+size_t emu_fastq_emit_grouped_work_bytes(int64_t, int) { return 16; }
+EMU_TWIN(fastq_emit_grouped_work_bytes);
+
 int emu_fastq_emit_grouped(const uint8_t *bytes, const atr_fastq_record *records, const int32_t *begin, const int32_t *end,
                            const int32_t *ubegin, const int32_t *uend, const int32_t *group, int n_groups, int64_t n,
-                           int64_t *offsets, int64_t *group_offsets, uint8_t *out) {
+                           int, int64_t *offsets, int64_t *group_offsets, void *, uint8_t *out, void *) {
     if (n_groups > ATR_EMIT_MAX_GROUPS) return ATR_ERR_UNSUPPORTED;
     if (n < 0 || n_groups < 1 || !group_offsets || ((ubegin == nullptr) != (uend == nullptr))) return ATR_ERR_INVALID;
     const FastqRecord *recs = (const FastqRecord *)records;
@@ -43,13 +46,15 @@ int emu_fastq_emit_grouped(const uint8_t *bytes, const atr_fastq_record *records
     }
     return ATR_OK;
 }
+EMU_TWIN(fastq_emit_grouped);
 
 int emu_demux_groups(const uint8_t *dest, const uint8_t *matched, const int64_t *last_which, const int32_t *adapter_group,
-                     int n_adapters, int untrimmed_group, int64_t n, int32_t *group) {
+                     int n_adapters, int untrimmed_group, int64_t n, int32_t *group, void *) {
     if (n < 0 || n_adapters < 0) return ATR_ERR_INVALID;
     for (int64_t r = 0; r < n; ++r)
         group[r] = demux_group_one(dest[r], matched[r] != 0, last_which[r], adapter_group, n_adapters, untrimmed_group);
     return ATR_OK;
 }
+EMU_TWIN(demux_groups);
 
 }  // extern "C"

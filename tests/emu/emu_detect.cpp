@@ -8,7 +8,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "atropos_hip.h"
+#include "emu_abi.hpp"
 #include "detect_core.hpp"
 #include "fastq_core.hpp"
 
@@ -26,14 +26,34 @@ int emu_detect_create(const uint8_t *seqs, const int32_t *lens, int nseq, int km
     *out = T;
     return 0;
 }
+EMU_TWIN(detect_create);
 
 void emu_detect_destroy(void *h) { delete (DetectTables *)h; }
+EMU_TWIN(detect_destroy);
 
-int64_t emu_detect_counter_words(const void *h) { return DET_HDR + 4 * (int64_t)((const DetectTables *)h)->nseq; }
+int64_t emu_detect_counter_bytes(const void *h) { return 8 * (DET_HDR + 4 * (int64_t)((const DetectTables *)h)->nseq); }
+EMU_TWIN(detect_counter_bytes);
 
-// force_hash != 0: every read gets the same hash (the distinct pass must still be exact)
-int emu_detect_filter(const void *h, const uint8_t *bytes, const FastqRecord *recs, int64_t n, int longest, int32_t *kept,
-                      int64_t *hashes, uint64_t *counters, int force_hash) {
+int emu_detect_clear(const void *h, void *counters, void *) {
+    memset(counters, 0, (size_t)emu_detect_counter_bytes(h));
+    return 0;
+}
+EMU_TWIN(detect_clear);
+
+int emu_detect_read(const void *h, const void *counters, uint64_t *out, void *) {
+    memcpy(out, counters, (size_t)emu_detect_counter_bytes(h));
+    return 0;
+}
+EMU_TWIN(detect_read);
+
+// test hook, != 0: every read gets the same hash (the distinct pass must still be exact)
+int emu_detect_force_hash = 0;
+
+int emu_detect_filter_batch(const void *h, const uint8_t *bytes, const atr_fastq_record *records, int64_t n, int longest,
+                            int32_t *kept, int64_t *hashes, void *d_counters, void *) {
+    const FastqRecord *recs = (const FastqRecord *)records;
+    uint64_t *counters = (uint64_t *)d_counters;
+    const int force_hash = emu_detect_force_hash;
     const DetectTables &T = *(const DetectTables *)h;
     if (n < 0 || longest < 0) return -1;
     if (longest > T.max_len) return -2;
@@ -65,14 +85,16 @@ int emu_detect_filter(const void *h, const uint8_t *bytes, const FastqRecord *re
     }
     return 0;
 }
+EMU_TWIN(detect_filter_batch);
 
 static bool same(const uint8_t *bytes, const FastqRecord *recs, const int32_t *kept, int64_t a, int64_t b) {
     return kept[a] == kept[b] && memcmp(bytes + recs[a].seq_off, bytes + recs[b].seq_off, (size_t)kept[a]) == 0;
 }
 
-int emu_detect_mark(const void *h, const uint8_t *bytes, const FastqRecord *recs, const int32_t *kept, const int64_t *order,
-                    const int64_t *head, int64_t m, uint8_t *rep, uint64_t *counters) {
-    (void)h;
+int emu_detect_mark_batch(const void *, const uint8_t *bytes, const atr_fastq_record *records, const int32_t *kept,
+                          const int64_t *order, const int64_t *head, int64_t m, uint8_t *rep, void *d_counters, void *) {
+    const FastqRecord *recs = (const FastqRecord *)records;
+    uint64_t *counters = (uint64_t *)d_counters;
     for (int64_t i = 0; i < m; ++i) {
         bool is_rep = true;
         const int64_t hd = head[i], r = order[i];
@@ -87,9 +109,12 @@ int emu_detect_mark(const void *h, const uint8_t *bytes, const FastqRecord *recs
     }
     return 0;
 }
+EMU_TWIN(detect_mark_batch);
 
-int emu_detect_match(const void *h, const uint8_t *bytes, const FastqRecord *recs, const int32_t *kept, const int64_t *order,
-                     const uint8_t *rep, int64_t m, uint64_t *counters) {
+int emu_detect_batch(const void *h, const uint8_t *bytes, const atr_fastq_record *records, const int32_t *kept,
+                     const int64_t *order, const uint8_t *rep, int64_t m, void *d_counters, void *) {
+    const FastqRecord *recs = (const FastqRecord *)records;
+    uint64_t *counters = (uint64_t *)d_counters;
     const DetectTables &T = *(const DetectTables *)h;
     const int S = T.nseq, W = T.words, stride = 2 * W + 1;
     std::vector<uint32_t> bits((size_t)S * stride);
@@ -136,5 +161,6 @@ int emu_detect_match(const void *h, const uint8_t *bytes, const FastqRecord *rec
     }
     return 0;
 }
+EMU_TWIN(detect_batch);
 
 }  // extern "C"

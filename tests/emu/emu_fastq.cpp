@@ -7,7 +7,7 @@
 #include <limits.h>
 #include <vector>
 
-#include "atropos_hip.h"
+#include "emu_abi.hpp"
 #include "locate_core.hpp"
 #include "fastq_core.hpp"
 #include "misc_core.hpp"
@@ -16,16 +16,20 @@ using namespace atr;
 
 extern "C" {
 
-int emu_fastq_count_lines(const uint8_t *bytes, int64_t nbytes, int64_t *nlines) {
+size_t emu_fastq_work_bytes(int64_t) { return 16; }
+EMU_TWIN(fastq_work_bytes);
+
+int emu_fastq_count_lines(const uint8_t *bytes, int64_t nbytes, void *, int64_t *nlines, void *) {
     if (nbytes < 0 || nbytes >= (int64_t)0xFFFFFFF0ll || !nlines) return ATR_ERR_INVALID;
     int64_t c = 0;
     for (int64_t i = 0; i < nbytes; ++i) c += is_line_end(bytes[i], i + 1 < nbytes ? bytes[i + 1] : 0) ? 1 : 0;
     *nlines = c;
     return ATR_OK;
 }
+EMU_TWIN(fastq_count_lines);
 
-int emu_fastq_index(const uint8_t *bytes, int64_t nbytes, uint32_t *line_ends, int64_t nlines,
-                    atr_fastq_record *records, int64_t *error) {
+int emu_fastq_index(const uint8_t *bytes, int64_t nbytes, const void *, uint32_t *line_ends, int64_t nlines,
+                    atr_fastq_record *records, int64_t *error, void *) {
     if (nbytes < 0 || nlines < 0 || !error) return ATR_ERR_INVALID;
     *error = LLONG_MAX;
     int64_t k = 0;
@@ -39,10 +43,11 @@ int emu_fastq_index(const uint8_t *bytes, int64_t nbytes, uint32_t *line_ends, i
     }
     return ATR_OK;
 }
+EMU_TWIN(fastq_index);
 
 int emu_pack_records(const uint8_t *bytes, const atr_fastq_record *records, const int32_t *begin, const int32_t *end,
                      int64_t nreads, int max_len, const uint8_t table[256], int planes, uint8_t *packed, int32_t *lens,
-                     int32_t *invalid) {
+                     int32_t *invalid, void *) {
     if (nreads < 0 || max_len < 0 || max_len > ATR_MAX_READ_LEN || !table) return ATR_ERR_INVALID;
     const int nchunks = (max_len + 31) / 32;
     uint32_t *out = (uint32_t *)packed;
@@ -70,8 +75,9 @@ int emu_pack_records(const uint8_t *bytes, const atr_fastq_record *records, cons
     }
     return ATR_OK;
 }
+EMU_TWIN(pack_records);
 
-int emu_clip_batch(const atr_fastq_record *, int32_t *begin, int32_t *end, int64_t n, int front, int back) {
+int emu_clip_batch(const atr_fastq_record *, int32_t *begin, int32_t *end, int64_t n, int front, int back, void *) {
     if (n < 0 || front < 0 || back > 0) return ATR_ERR_INVALID;
     for (int64_t r = 0; r < n; ++r) {
         const int a = begin[r], b = end[r];
@@ -83,9 +89,10 @@ int emu_clip_batch(const atr_fastq_record *, int32_t *begin, int32_t *end, int64
     }
     return ATR_OK;
 }
+EMU_TWIN(clip_batch);
 
 int emu_quality_trim_batch(const uint8_t *bytes, const atr_fastq_record *records, int32_t *begin, int32_t *end,
-                           int64_t n, int cutoff_front, int cutoff_back, int base, int nextseq) {
+                           int64_t n, int cutoff_front, int cutoff_back, int base, int nextseq, void *) {
     for (int64_t r = 0; r < n; ++r) {
         const FastqRecord &rec = *(const FastqRecord *)&records[r];
         const int a = begin[r], b = end[r];
@@ -102,9 +109,10 @@ int emu_quality_trim_batch(const uint8_t *bytes, const atr_fastq_record *records
     }
     return ATR_OK;
 }
+EMU_TWIN(quality_trim_batch);
 
 int emu_nend_trim_batch(const uint8_t *bytes, const atr_fastq_record *records, int32_t *begin, int32_t *end,
-                        const int32_t *ubegin, const int32_t *uend, int64_t n) {
+                        const int32_t *ubegin, const int32_t *uend, int64_t n, void *) {
     for (int64_t r = 0; r < n; ++r) {
         const FastqRecord &rec = *(const FastqRecord *)&records[r];
         const int a = begin[r], b = end[r];
@@ -117,9 +125,11 @@ int emu_nend_trim_batch(const uint8_t *bytes, const atr_fastq_record *records, i
     }
     return ATR_OK;
 }
+EMU_TWIN(nend_trim_batch);
 
-int emu_match_trim_batch(const int16_t *matches, const uint8_t *front, int default_front, int32_t *begin, int32_t *end,
-                         uint8_t *active, uint8_t *matched, int64_t n) {
+int emu_match_trim_batch(const atr_result *records, const uint8_t *front, int default_front, int32_t *begin, int32_t *end,
+                         uint8_t *active, uint8_t *matched, int64_t n, void *) {
+    const int16_t *matches = (const int16_t *)records;
     for (int64_t r = 0; r < n; ++r) {
         if (active && !active[r]) continue;
         const int16_t *m = matches + 8 * r;
@@ -134,11 +144,12 @@ int emu_match_trim_batch(const int16_t *matches, const uint8_t *front, int defau
     }
     return ATR_OK;
 }
+EMU_TWIN(match_trim_batch);
 
 int emu_read_filter_batch(const uint8_t *bytes, const atr_fastq_record *records, const int32_t *begin,
                           const int32_t *end, const int32_t *ubegin, const int32_t *uend, const uint8_t *matched,
                           int64_t n, int min_len, int max_len, double max_n, int discard_trimmed, int discard_untrimmed,
-                          uint8_t *dest, uint8_t *fail_mask) {
+                          uint8_t *dest, uint8_t *fail_mask, void *) {
     for (int64_t r = 0; r < n; ++r) {
         const FastqRecord &rec = *(const FastqRecord *)&records[r];
         const int a = begin[r], b = end[r] > a ? end[r] : a;
@@ -150,19 +161,22 @@ int emu_read_filter_batch(const uint8_t *bytes, const atr_fastq_record *records,
     }
     return ATR_OK;
 }
+EMU_TWIN(read_filter_batch);
 
-int emu_pair_filter_batch(const uint8_t *mask1, const uint8_t *mask2, int64_t n, int min_affected, uint8_t *dest) {
+int emu_pair_filter_batch(const uint8_t *mask1, const uint8_t *mask2, int64_t n, int min_affected, uint8_t *dest, void *) {
     if (min_affected != 1 && min_affected != 2) return ATR_ERR_INVALID;
     for (int64_t r = 0; r < n; ++r) dest[r] = (uint8_t)filter_destination(mask1[r], mask2[r], true, min_affected);
     return ATR_OK;
 }
+EMU_TWIN(pair_filter_batch);
 
-int emu_insert_plan_batch(const int16_t *ins, const int16_t *fb1, const int16_t *fb2, uint8_t *bytes1,
+int emu_insert_plan_batch(const atr_result *insert, const atr_result *fallback1, const atr_result *fallback2, uint8_t *bytes1,
                           const atr_fastq_record *records1, uint8_t *bytes2, const atr_fastq_record *records2,
                           int32_t *begin1, int32_t *end1, int32_t *begin2, int32_t *end2, int32_t *uend1, int32_t *uend2,
                           int64_t n, int min_insert_len, int symmetric, int trim_action, int correct_action,
                           int min_qual_diff, const uint8_t *comp, uint8_t *matched1, uint8_t *matched2,
-                          int32_t *corrected, int64_t *error) {
+                          int32_t *corrected, int64_t *error, void *) {
+    const int16_t *ins = (const int16_t *)insert, *fb1 = (const int16_t *)fallback1, *fb2 = (const int16_t *)fallback2;
     if (error) *error = LLONG_MAX;
     for (int64_t r = 0; r < n; ++r) {
         const int a1 = begin1[r], a2 = begin2[r];
@@ -195,28 +209,38 @@ int emu_insert_plan_batch(const int16_t *ins, const int16_t *fb1, const int16_t 
     }
     return ATR_OK;
 }
+EMU_TWIN(insert_plan_batch);
 
-// atr_merge_plan_batch + atr_merge_emit_batch in one call: out == NULL sizes the output
-// (offsets[n + 1], kind[n]); with out the text is written (mate bases, correction, the rest).
-int emu_merge_batch(const int16_t *align, const int32_t *need, const uint8_t *insert_matched, uint8_t *bytes1,
-                    const atr_fastq_record *records1, uint8_t *bytes2, const atr_fastq_record *records2,
-                    const int32_t *begin1, const int32_t *end1, const int32_t *begin2, const int32_t *end2, int64_t n,
-                    int correct_action, int min_qual_diff, const uint8_t *comp, uint8_t *kind, int64_t *offsets,
-                    int32_t *corrected, int64_t *error, uint8_t *out) {
-    if (!out) {
-        *error = LLONG_MAX;
-        int64_t at = 0;
-        for (int64_t r = 0; r < n; ++r) {
-            const int len1 = std::max(0, end1[r] - begin1[r]), len2 = std::max(0, end2[r] - begin2[r]);
-            const MergeShape m = merge_shape(align + 8 * r, len1, len2, need[r]);
-            kind[r] = (uint8_t)m.kind;
-            offsets[r] = at;
-            if (m.kind == MERGE_INVALID) *error = std::min<int64_t>(*error, r * 8 + 4);
-            else if (m.kind != MERGE_NONE) at += fastq_record_bytes(*(const FastqRecord *)&records1[r], m.len[0] + m.len[1]);
-        }
-        offsets[n] = at;
-        return ATR_OK;
+size_t emu_merge_work_bytes(int64_t) { return 16; }
+EMU_TWIN(merge_work_bytes);
+
+// sizes the output: kind[n], offsets[n + 1]
+int emu_merge_plan_batch(const atr_result *records, const int32_t *need, const atr_fastq_record *records1, const int32_t *begin1,
+                         const int32_t *end1, const int32_t *begin2, const int32_t *end2, int64_t n, uint8_t *kind,
+                         int64_t *offsets, void *, int64_t *error, void *) {
+    const int16_t *align = (const int16_t *)records;
+    *error = LLONG_MAX;
+    int64_t at = 0;
+    for (int64_t r = 0; r < n; ++r) {
+        const int len1 = std::max(0, end1[r] - begin1[r]), len2 = std::max(0, end2[r] - begin2[r]);
+        const MergeShape m = merge_shape(align + 8 * r, len1, len2, need[r]);
+        kind[r] = (uint8_t)m.kind;
+        offsets[r] = at;
+        if (m.kind == MERGE_INVALID) *error = std::min<int64_t>(*error, r * 8 + 4);
+        else if (m.kind != MERGE_NONE) at += fastq_record_bytes(*(const FastqRecord *)&records1[r], m.len[0] + m.len[1]);
     }
+    offsets[n] = at;
+    return ATR_OK;
+}
+EMU_TWIN(merge_plan_batch);
+
+// writes the text: mate bases, correction, the rest
+int emu_merge_emit_batch(const atr_result *records, const uint8_t *kind, const uint8_t *insert_matched, uint8_t *bytes1,
+                         const atr_fastq_record *records1, uint8_t *bytes2, const atr_fastq_record *records2,
+                         const int32_t *begin1, const int32_t *end1, const int32_t *begin2, const int32_t *end2, int64_t n,
+                         int correct_action, int min_qual_diff, const uint8_t *comp, const int64_t *offsets,
+                         int32_t *corrected, int64_t *error, uint8_t *out, void *) {
+    const int16_t *align = (const int16_t *)records;
     for (int pass = 0; pass < 3; ++pass)
         for (int64_t r = 0; r < n; ++r) {
             if (kind[r] == MERGE_NONE || kind[r] == MERGE_INVALID) continue;
@@ -239,10 +263,14 @@ int emu_merge_batch(const int16_t *align, const int32_t *need, const uint8_t *in
         }
     return ATR_OK;
 }
+EMU_TWIN(merge_emit_batch);
+
+size_t emu_fastq_emit_work_bytes(int64_t) { return 16; }
+EMU_TWIN(fastq_emit_work_bytes);
 
 int emu_fastq_emit(const uint8_t *bytes, const atr_fastq_record *records, const int32_t *begin, const int32_t *end,
-                   const int32_t *ubegin, const int32_t *uend, const uint8_t *dest, int which, int64_t n,
-                   int64_t *offsets, uint8_t *out) {
+                   const int32_t *ubegin, const int32_t *uend, const uint8_t *dest, int which, int64_t n, int,
+                   int64_t *offsets, void *, uint8_t *out, void *) {
     if (!out) {
         int64_t run = 0;
         for (int64_t r = 0; r < n; ++r) {
@@ -277,5 +305,6 @@ int emu_fastq_emit(const uint8_t *bytes, const atr_fastq_record *records, const 
     }
     return ATR_OK;
 }
+EMU_TWIN(fastq_emit);
 
 }  // extern "C"

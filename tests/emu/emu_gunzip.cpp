@@ -5,7 +5,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "atropos_hip.h"
+#include "emu_abi.hpp"
 #include "inflate_core.hpp"
 
 using namespace atr;
@@ -18,9 +18,10 @@ int emu_bgzf_scan(const uint8_t *buf, int64_t n_bytes, int64_t max_members, int6
     if (n_bytes > 0 && !buf) return ATR_ERR_INVALID;
     return inf_scan(buf, n_bytes, max_members, member_at, text_at, n_members, covered) ? ATR_ERR_INVALID : ATR_OK;
 }
+EMU_TWIN(bgzf_scan);
 
 int emu_gunzip_members(const uint8_t *stream, int64_t n_stream, const int64_t *member_at, const int64_t *text_at,
-                       int64_t n_members, uint8_t *text, int64_t text_capacity, int32_t *status, int32_t *bad) {
+                       int64_t n_members, uint8_t *text, int64_t text_capacity, int32_t *status, int32_t *bad, void *) {
     if (n_stream < 0 || n_members < 0 || text_capacity < 0) return ATR_ERR_INVALID;
     if (n_stream >= ((int64_t)1 << 32) || text_capacity >= ((int64_t)1 << 32) || n_members > INF_MAX_MEMBERS) return ATR_ERR_UNSUPPORTED;
     if (n_members * 26 > n_stream) return ATR_ERR_INVALID;
@@ -46,5 +47,6 @@ int emu_gunzip_members(const uint8_t *stream, int64_t n_stream, const int64_t *m
     }
     return ATR_OK;
 }
+EMU_TWIN(gunzip_members);
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "atropos_hip.h"
+#include "emu_abi.hpp"
 #include "deflate_core.hpp"
 
 using namespace atr;
@@ -13,17 +13,20 @@ using namespace atr;
 extern "C" {
 
 int64_t emu_gzip_bound(int64_t n_bytes) { return n_bytes < 0 ? (int64_t)ATR_ERR_INVALID : gz_bound(n_bytes); }
+EMU_TWIN(gzip_bound);
 
 size_t emu_gzip_work_bytes(int64_t n_bytes) { return n_bytes < 0 ? 0 : (size_t)gz_work_bytes(n_bytes); }
+EMU_TWIN(gzip_work_bytes);
 
 int emu_gzip_eof(uint8_t *buf28) {
     if (!buf28) return ATR_ERR_INVALID;
     gz_eof_member(buf28);
     return 28;
 }
+EMU_TWIN(gzip_eof);
 
 int emu_gzip_blocks(const uint8_t *text, int64_t n_bytes, uint8_t *out, int64_t out_capacity, int64_t *total,
-                    int64_t *member_offsets, void *work_buf) {
+                    int64_t *member_offsets, void *work_buf, void *) {
     if (n_bytes < 0 || out_capacity < 0) return ATR_ERR_INVALID;
     if (n_bytes >= ((int64_t)1 << 32)) return ATR_ERR_UNSUPPORTED;
     if (out_capacity < gz_bound(n_bytes)) return ATR_ERR_INVALID;
@@ -62,6 +65,7 @@ int emu_gzip_blocks(const uint8_t *text, int64_t n_bytes, uint8_t *out, int64_t 
     *total = run;
     return ATR_OK;
 }
+EMU_TWIN(gzip_blocks);
 
 // gz_build_lengths driven directly (the code-length fuzz of test_gzip_host.py): freq[n] in ascending order, nonzero;
 // len_out[i] is the length of freq[i], blc_out[0 .. 15] the codes per length.

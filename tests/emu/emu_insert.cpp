@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "insert_host.hpp"
+#include "emu_abi.hpp"
 
 using namespace atr;
 
@@ -81,16 +82,19 @@ int emu_insert_aligner_create(const atr_insert_config *cfg, atr_insert_aligner *
     *out = h;
     return ATR_OK;
 }
+EMU_TWIN(insert_aligner_create);
 
 void emu_insert_aligner_destroy(atr_insert_aligner *a) { delete a; }
+EMU_TWIN(insert_aligner_destroy);
 
 int emu_case_sensitive_table(uint8_t table[256]) {
     case_sensitive_table(tables().dna15, table);
     return ATR_OK;
 }
+EMU_TWIN(case_sensitive_table);
 
-int emu_insert_match_batch(const atr_insert_aligner *a, const uint8_t *p1, const int32_t *l1, const uint8_t *p2,
-                           const int32_t *l2, int64_t npairs, int max_len, int cased, int16_t *out) {
+int emu_insert_match_batch_coded(const atr_insert_aligner *a, const uint8_t *p1, const int32_t *l1, const uint8_t *p2,
+                                 const int32_t *l2, int64_t npairs, int max_len, int cased, atr_result *out, void *) {
     if (!a || npairs < 0 || max_len < 0) return ATR_ERR_INVALID;
     if (cased && !a->cased_ok) return ATR_ERR_UNSUPPORTED;
     if (max_len > ATR_INSERT_MAX_READ) return ATR_ERR_UNSUPPORTED;
@@ -111,5 +115,6 @@ int emu_insert_match_batch(const atr_insert_aligner *a, const uint8_t *p1, const
     }
     return ATR_OK;
 }
+EMU_TWIN(insert_match_batch_coded);
 
 }  // extern "C"

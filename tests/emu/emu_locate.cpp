@@ -15,6 +15,7 @@
 #include "piece_core.hpp"
 #include "linked_host.hpp"
 #include "wave_core.hpp"
+#include "emu_abi.hpp"
 
 using namespace atr;
 
@@ -434,17 +435,28 @@ int emu_aligner_create(const char *ref, int m, double e, int flags, int wr, int 
                        int indel_cost, atr_aligner **out) {
     return aligner_create(ref, m, e, flags, wr, wq, min_overlap, indel_cost, out);
 }
+EMU_TWIN(aligner_create);
 void emu_aligner_destroy(atr_aligner *a) { delete a; }
+EMU_TWIN(aligner_destroy);
 int emu_aligner_set_min_overlap(atr_aligner *a, int v) { return aligner_set_min_overlap(a, v); }
+EMU_TWIN(aligner_set_min_overlap);
 int emu_aligner_set_indel_cost(atr_aligner *a, int v) { return aligner_set_indel_cost(a, v); }
+EMU_TWIN(aligner_set_indel_cost);
 int emu_aligner_query_table(const atr_aligner *a, uint8_t table[256]) {
     if (table) memcpy(table, a->qtable, 256);
     return a->table_kind;
 }
+EMU_TWIN(aligner_query_table);
 size_t emu_packed_bytes(int64_t nreads, int max_len) { return packed_bytes(nreads, max_len); }
+EMU_TWIN(packed_bytes);
+// the twins take the scratch of the kernels they stand in for and leave it alone
+size_t emu_locate_work_bytes(int64_t) { return 16; }
+EMU_TWIN(locate_work_bytes);
+size_t emu_linked_work_bytes(const atr_linked_set *, int64_t) { return 16; }
+EMU_TWIN(linked_work_bytes);
 
 int emu_pack_reads(const uint8_t *ascii, int64_t row_stride, const int32_t *lens, const int32_t *starts,
-                   int64_t nreads, int max_len, const uint8_t table[256], uint8_t *packed, int32_t *invalid) {
+                   int64_t nreads, int max_len, const uint8_t table[256], uint8_t *packed, int32_t *invalid, void *) {
     const int nchunks = (max_len + 31) / 32;
     const long long ntiles = (nreads + 63) / 64;
     uint32_t *dst = (uint32_t *)packed;
@@ -463,10 +475,11 @@ int emu_pack_reads(const uint8_t *ascii, int64_t row_stride, const int32_t *lens
         }
     return ATR_OK;
 }
+EMU_TWIN(pack_reads);
 
 // atr_pack_planes: plane64 layout (bit planes of the codes, 32 bases per 16-byte chunk)
 int emu_pack_planes(const uint8_t *ascii, int64_t row_stride, const int32_t *lens, const int32_t *starts,
-                    int64_t nreads, int max_len, const uint8_t table[256], uint8_t *packed, int32_t *invalid) {
+                    int64_t nreads, int max_len, const uint8_t table[256], uint8_t *packed, int32_t *invalid, void *) {
     const int nchunks = (max_len + 31) / 32;
     const long long ntiles = (nreads + 63) / 64;
     uint32_t *dst = (uint32_t *)packed;
@@ -485,10 +498,11 @@ int emu_pack_planes(const uint8_t *ascii, int64_t row_stride, const int32_t *len
         }
     return ATR_OK;
 }
+EMU_TWIN(pack_planes);
 
 // atr_planes_count_uncoded
 int emu_planes_count_uncoded(const uint8_t *planes, const int32_t *lens, const int32_t *other, int64_t nreads, int max_len,
-                             int32_t *count) {
+                             int32_t *count, void *) {
     const int nchunks = (max_len + 31) / 32;
     const uint32_t *src = (const uint32_t *)planes;
     for (long long r = 0; r < nreads; ++r) {
@@ -504,6 +518,7 @@ int emu_planes_count_uncoded(const uint8_t *planes, const int32_t *lens, const i
     }
     return ATR_OK;
 }
+EMU_TWIN(planes_count_uncoded);
 
 }  // extern "C"
 
@@ -526,8 +541,11 @@ int emu_linked_create(const atr_linked_adapter *adapters, int n, atr_linked_set 
     *out = s;
     return ATR_OK;
 }
+EMU_TWIN(linked_create);
 void emu_linked_destroy(atr_linked_set *s) { delete s; }
+EMU_TWIN(linked_destroy);
 int emu_linked_query_table(const atr_linked_set *s) { return s ? s->table_kind : ATR_ERR_INVALID; }
+EMU_TWIN(linked_query_table);
 }  // extern "C"
 
 // atr_linked_match_batch (linked_kernels.hip), read by read with the kernels' per-lane functions
@@ -607,7 +625,7 @@ static void emu_linked_l1(const atr_linked_set *s, const uint32_t *pk, const int
 
 extern "C" {
 int emu_linked_match_batch(const atr_linked_set *s, const uint8_t *packed, const int32_t *lens, int64_t nreads,
-                           int max_len, int8_t *which_out, int16_t *front, int16_t *back) {
+                           int max_len, int8_t *which_out, atr_result *front, atr_result *back, void *, void *) {
     if (!s || nreads < 0 || max_len < 0 || max_len > ATR_MAX_READ_LEN) return ATR_ERR_INVALID;
     if (nreads == 0) return ATR_OK;
     if (max_len == 0) return ATR_ERR_UNSUPPORTED;
@@ -634,6 +652,7 @@ int emu_linked_match_batch(const atr_linked_set *s, const uint8_t *packed, const
     }
     return ATR_OK;
 }
+EMU_TWIN(linked_match_batch);
 
 }  // extern "C"
 
@@ -743,8 +762,8 @@ static void emu_wave_read_r(const atr_aligner *a, const uint32_t *pk, int nchunk
 
 extern "C" {
 
-int emu_locate_batch(const atr_aligner *a, const uint8_t *packed, const int32_t *lens, int64_t nreads,
-                     int max_len, int16_t *out, int path) {
+int emu_locate_batch_path(const atr_aligner *a, const uint8_t *packed, const int32_t *lens, int64_t nreads,
+                          int max_len, atr_result *out, void *, int path, void *) {
     if (!a || nreads < 0 || max_len < 0 || max_len > ATR_MAX_LONG_READ_LEN) return ATR_ERR_INVALID;
     if (path < ATR_LOCATE_AUTO || path > ATR_LOCATE_WAVE) return ATR_ERR_INVALID;
     if (path == ATR_LOCATE_WAVE && (a->p.m > WAVE_MAX_M || max_len > ATR_MAX_READ_LEN)) return ATR_ERR_UNSUPPORTED;
@@ -795,6 +814,7 @@ int emu_locate_batch(const atr_aligner *a, const uint8_t *packed, const int32_t 
     fn(a, (const uint32_t *)packed, lens, nreads, (max_len + 31) / 32, max_len, (uint32_t *)out);
     return ATR_OK;
 }
+EMU_TWIN(locate_batch_path);
 
 // atr_locate_planes_applies / atr_locate_planes_batch (the emulation takes every word count up to 10)
 int emu_locate_planes_applies(const atr_aligner *a, int max_len, int ragged) {
@@ -807,6 +827,7 @@ int emu_locate_planes_applies(const atr_aligner *a, int max_len, int ragged) {
     const int nw = (max_len + 31) / 32;
     return (nw >= 3 && nw <= 10) ? 1 : 0;
 }
+EMU_TWIN(locate_planes_applies);
 int emu_locate_planes_all_widths(const atr_aligner *a, int max_len, int ragged) {          // the envelope without the instantiated widths
     if (!a || !a->filterable || max_len < 1 || max_len > 32 * PIECE_MAX_WORDS) return 0;
     if (ragged) max_len = 32 * ((max_len + 31) / 32);
@@ -828,7 +849,7 @@ void emu_piece_stats(long long out[18], int reset) {
 }
 
 int emu_locate_planes_batch(const atr_aligner *a, const uint8_t *planes, const int32_t *lens, int64_t nreads, int max_len,
-                            int16_t *out) {
+                            atr_result *out, void *, void *) {
     if (!a || nreads < 0 || max_len < 0 || max_len > ATR_MAX_READ_LEN) return ATR_ERR_INVALID;
     if (nreads == 0) return ATR_OK;
     if (!emu_locate_planes_all_widths(a, max_len, lens != nullptr)) return ATR_ERR_UNSUPPORTED;
@@ -838,5 +859,6 @@ int emu_locate_planes_batch(const atr_aligner *a, const uint8_t *planes, const i
     fn(a, (const uint32_t *)planes, lens, nreads, (max_len + 31) / 32, max_len, (uint32_t *)out);
     return ATR_OK;
 }
+EMU_TWIN(locate_planes_batch);
 
 }  // extern "C"

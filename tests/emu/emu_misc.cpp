@@ -12,6 +12,7 @@
 #include "pairs_fast_core.hpp"
 #include "pairs_long_core.hpp"
 #include "wave_core.hpp"
+#include "emu_abi.hpp"
 
 using namespace atr;
 
@@ -20,11 +21,13 @@ extern "C" {
 size_t emu_multi_locate_work_bytes(int64_t npairs, int max_ref_len) {
     return (size_t)npairs * 3 * ((size_t)max_ref_len + 1) * sizeof(int32_t);
 }
+EMU_TWIN(multi_locate_work_bytes);
 
 int emu_multi_locate_batch(const uint8_t *refs, int64_t ref_stride, const int32_t *ref_lens, const uint8_t *queries,
                            int64_t q_stride, const int32_t *q_lens, int64_t npairs, double e, int flags,
-                           int min_overlap, int max_matches, int max_ref_len, void *work, int16_t *out,
-                           int32_t *counts, int out_stride) {
+                           int min_overlap, int max_matches, int max_ref_len, void *work, atr_result *records,
+                           int32_t *counts, int out_stride, void *) {
+    int16_t *out = (int16_t *)records;
     if (npairs < 0 || flags < 0 || flags > 15 || max_matches < 1 || out_stride < 1) return ATR_ERR_INVALID;
     (void)max_ref_len;
     std::vector<int16_t> dp((size_t)out_stride * 8);
@@ -47,7 +50,8 @@ int emu_multi_locate_batch(const uint8_t *refs, int64_t ref_stride, const int32_
 }
 
 int emu_compare_batch(const char *ref, int m, const uint8_t *queries, int64_t q_stride, const int32_t *lens,
-                      int64_t n, int max_len, int wildcard_ref, int wildcard_query, int suffix, int16_t *out) {
+                      int64_t n, int max_len, int wildcard_ref, int wildcard_query, int suffix, atr_result *records, void *) {
+    int16_t *out = (int16_t *)records;
     if (!ref || m < 0 || n < 0) return ATR_ERR_INVALID;
     if (m > 1024) return ATR_ERR_UNSUPPORTED;
     const Tables &T = tables();
@@ -60,8 +64,14 @@ int emu_compare_batch(const char *ref, int m, const uint8_t *queries, int64_t q_
     return ATR_OK;
 }
 
-// atr_locate_debug
-int emu_locate_debug(const atr_aligner *a, const uint32_t *packed, int n, int32_t *matrix, int16_t *rec) {
+// atr_locate_debug: the scratch is the matrix alone
+size_t emu_locate_debug_bytes(const atr_aligner *a, int n) { return a && n >= 0 ? 4 * ((size_t)a->p.m + 1) * ((size_t)n + 1) : 0; }
+EMU_TWIN(locate_debug_bytes);
+
+int emu_locate_debug(const atr_aligner *a, const uint8_t *d_packed, int n, void *d_matrix, atr_result *d_out, void *) {
+    const uint32_t *packed = (const uint32_t *)d_packed;
+    int32_t *matrix = (int32_t *)d_matrix;
+    int16_t *rec = (int16_t *)d_out;
     if (!a || n < 0) return ATR_ERR_INVALID;
     const LocateParams &lp = a->p;
     const int p0 = round_up_rows(lp.m) - lp.m;
@@ -72,10 +82,13 @@ int emu_locate_debug(const atr_aligner *a, const uint32_t *packed, int n, int32_
                      col.data(), matrix, rec);
     return ATR_OK;
 }
+EMU_TWIN(locate_debug);
 
 // atr_compare_packed
-int emu_compare_packed(const atr_aligner *a, const uint32_t *packed, const int32_t *lens, int64_t n, int max_len, int suffix,
-                       int16_t *out) {
+int emu_compare_packed(const atr_aligner *a, const uint8_t *d_packed, const int32_t *lens, int64_t n, int max_len, int suffix,
+                       atr_result *records, void *) {
+    const uint32_t *packed = (const uint32_t *)d_packed;
+    int16_t *out = (int16_t *)records;
     if (!a || n < 0 || max_len < 0) return ATR_ERR_INVALID;
     if (max_len > ATR_MAX_READ_LEN) return ATR_ERR_UNSUPPORTED;
     const int nchunks = (max_len + 31) / 32;
@@ -88,19 +101,23 @@ int emu_compare_packed(const atr_aligner *a, const uint32_t *packed, const int32
     return ATR_OK;
 }
 
-int emu_adapter_postfilter(int16_t *rec, int64_t n, int m, int min_overlap, double max_error_rate,
-                           const double *rmp, int rmp_ld, double max_rmp, int accept_full) {
+int emu_adapter_postfilter(atr_result *records, int64_t n, int m, int min_overlap, double max_error_rate,
+                           const double *rmp, int rmp_ld, double max_rmp, int accept_full, void *) {
+    int16_t *rec = (int16_t *)records;
     for (int64_t p = 0; p < n; ++p)
         adapter_postfilter_one(rec + 8 * p, m, min_overlap, max_error_rate, rmp, rmp_ld, max_rmp, accept_full != 0);
     return ATR_OK;
 }
+EMU_TWIN(adapter_postfilter);
 
 // atr_insert_correct_batch: gated on the insert-match records; with the plane buffers the
 // plane-guided walk of correct_planes_kernel, else the byte walk
-int emu_insert_correct_batch(const int16_t *records, const uint32_t *planes1, const uint32_t *planes2, int planes_max_len,
+int emu_insert_correct_batch(const atr_result *insert_records, const uint8_t *d_planes1, const uint8_t *d_planes2, int planes_max_len,
                              uint8_t *s1, uint8_t *q1, const int32_t *l1, uint8_t *s2, uint8_t *q2, const int32_t *l2,
                              int64_t stride, int64_t n, int max_len, int action, int min_qual_diff, const uint8_t *comp,
-                             int32_t *changed, int32_t *newlen) {
+                             int32_t *changed, int32_t *newlen, void *) {
+    const int16_t *records = (const int16_t *)insert_records;
+    const uint32_t *planes1 = (const uint32_t *)d_planes1, *planes2 = (const uint32_t *)d_planes2;
     const int nchunks = (planes_max_len + 31) / 32;
     for (int64_t p = 0; p < n; ++p) {
         const int len1 = l1 ? l1[p] : max_len, len2 = l2 ? l2[p] : max_len;
@@ -142,7 +159,7 @@ int emu_insert_correct_batch(const int16_t *records, const uint32_t *planes1, co
 int emu_correct_errors_batch(uint8_t *s1, uint8_t *q1, const int32_t *l1, uint8_t *s2, uint8_t *q2,
                              const int32_t *l2, int64_t stride, const int16_t *im, const uint8_t *mask, int64_t n,
                              int max_len, int action, int min_qual_diff, int truncate, const uint8_t comp[256],
-                             int32_t *changed, int32_t *newlen) {
+                             int32_t *changed, int32_t *newlen, void *) {
     if (n < 0 || action < 0 || action > 2 || !comp) return ATR_ERR_INVALID;
     if ((q1 == nullptr) != (q2 == nullptr)) return ATR_ERR_INVALID;
     if (action != 0 && !q1) return ATR_ERR_INVALID;
@@ -159,6 +176,11 @@ int emu_correct_errors_batch(uint8_t *s1, uint8_t *q1, const int32_t *l1, uint8_
     }
     return ATR_OK;
 }
+EMU_TWIN(multi_locate_batch);
+EMU_TWIN(compare_batch);
+EMU_TWIN(compare_packed);
+EMU_TWIN(insert_correct_batch);
+EMU_TWIN(correct_errors_batch);
 
 // atr_locate_pairs_batch: one pair after the other, column and staged reference in plain arrays
 // test hook: also exercise the LDS-column variant (the library's fallback when stream-ordered allocation is missing)
@@ -383,18 +405,16 @@ static void emu_pair_wave_r(const atr::PairParams &p, const uint32_t *rp, int m,
 
 extern "C" {
 
-int emu_pairs_path = 0;          // ATR_PAIRS_* of the next emu_locate_pairs_*_batch call (set by tests/emu/backend.py)
-
-int emu_locate_pairs_need_batch(const uint32_t *ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
-                                const uint32_t *qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs,
-                                double e, int flags, int wildcard_ref, int wildcard_query, int min_overlap, int indel_cost,
-                                const int32_t *need, uint32_t *out);
+size_t emu_locate_pairs_long_work_bytes(int64_t, int) { return 16; }
+EMU_TWIN(locate_pairs_long_work_bytes);
 
 // atr_locate_pairs_long_batch: pairs_long_core.hpp, one pair after the other
-int emu_locate_pairs_long_batch(const uint32_t *ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
-                                const uint32_t *qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs,
+int emu_locate_pairs_long_batch(const uint8_t *d_ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
+                                const uint8_t *d_qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs,
                                 double e, int flags, int wildcard_ref, int wildcard_query, int min_overlap, int indel_cost,
-                                uint32_t *out) {
+                                atr_result *records, void *, void *) {
+    const uint32_t *ref_packed = (const uint32_t *)d_ref_packed, *qry_packed = (const uint32_t *)d_qry_packed;
+    uint32_t *out = (uint32_t *)records;
     if (npairs < 0 || flags < 0 || flags > 15 || min_overlap < 1 || indel_cost < 1) return ATR_ERR_INVALID;
     if (ref_max_len > ATR_MAX_LONG_READ_LEN || qry_max_len > ATR_MAX_LONG_READ_LEN) return ATR_ERR_UNSUPPORTED;
     if (!(e >= 0.0) || e * (double)ref_max_len > (double)atr::PAIRS_LONG_MAX_K) return ATR_ERR_UNSUPPORTED;
@@ -413,19 +433,13 @@ int emu_locate_pairs_long_batch(const uint32_t *ref_packed, const int32_t *ref_l
     }
     return ATR_OK;
 }
+EMU_TWIN(locate_pairs_long_batch);
 
-int emu_locate_pairs_batch(const uint32_t *ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
-                           const uint32_t *qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs,
-                           double e, int flags, int wildcard_ref, int wildcard_query, int min_overlap, int indel_cost,
-                           uint32_t *out) {
-    return emu_locate_pairs_need_batch(ref_packed, ref_lens, ref_max_len, revcomp, qry_packed, qry_lens, qry_max_len, npairs, e,
-                                       flags, wildcard_ref, wildcard_query, min_overlap, indel_cost, nullptr, out);
-}
-
-int emu_locate_pairs_need_batch(const uint32_t *ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
-                                const uint32_t *qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs,
-                                double e, int flags, int wildcard_ref, int wildcard_query, int min_overlap, int indel_cost,
-                                const int32_t *need, uint32_t *out) {
+// atr_locate_pairs_*_batch: one body, the kernel family named by ``path`` (ATR_PAIRS_*)
+static int pairs_batch(const uint32_t *ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
+                       const uint32_t *qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs,
+                       double e, int flags, int wildcard_ref, int wildcard_query, int min_overlap, int indel_cost,
+                       const int32_t *need, int path, uint32_t *out) {
     if (npairs < 0) return ATR_ERR_INVALID;
     atr::PairParams p;
     const int rc = atr::pairs_params(e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost, ref_max_len,
@@ -433,7 +447,6 @@ int emu_locate_pairs_need_batch(const uint32_t *ref_packed, const int32_t *ref_l
     if (rc != ATR_OK) return rc;
     const int rch = (ref_max_len + 31) / 32, qch = (qry_max_len + 31) / 32;
     std::vector<uint32_t> col((size_t)ref_max_len + 1), refw((size_t)(ref_max_len + 7) / 8 + 1);
-    const int path = emu_pairs_path;
     if (path < ATR_PAIRS_AUTO || path > ATR_PAIRS_WAVE) return ATR_ERR_INVALID;
     if (path == ATR_PAIRS_WAVE && !atr::wave_pairs_applies(ref_max_len, 0)) return ATR_ERR_UNSUPPORTED;
     const bool wave = path == ATR_PAIRS_WAVE || (path == ATR_PAIRS_AUTO && atr::wave_pairs_applies(ref_max_len, npairs));
@@ -522,5 +535,37 @@ int emu_locate_pairs_need_batch(const uint32_t *ref_packed, const int32_t *ref_l
     }
     return ATR_OK;
 }
+
+int emu_locate_pairs_path_batch(const uint8_t *ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
+    const uint8_t *qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs, double e, int flags,
+    int wildcard_ref, int wildcard_query, int min_overlap, int indel_cost, const int32_t *need, int path, atr_result *out, void *) {
+    return pairs_batch((const uint32_t *)ref_packed, ref_lens, ref_max_len, revcomp, (const uint32_t *)qry_packed, qry_lens, qry_max_len,
+                     npairs, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost, need, path, (uint32_t *)out);
+}
+EMU_TWIN(locate_pairs_path_batch);
+
+int emu_locate_pairs_need_batch(const uint8_t *ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
+    const uint8_t *qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs, double e, int flags,
+    int wildcard_ref, int wildcard_query, int min_overlap, int indel_cost, const int32_t *need, atr_result *out, void *) {
+    return pairs_batch((const uint32_t *)ref_packed, ref_lens, ref_max_len, revcomp, (const uint32_t *)qry_packed, qry_lens, qry_max_len,
+                     npairs, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost, need, ATR_PAIRS_AUTO, (uint32_t *)out);
+}
+EMU_TWIN(locate_pairs_need_batch);
+
+int emu_locate_pairs_batch(const uint8_t *ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
+    const uint8_t *qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs, double e, int flags,
+    int wildcard_ref, int wildcard_query, int min_overlap, int indel_cost, atr_result *out, void *) {
+    return pairs_batch((const uint32_t *)ref_packed, ref_lens, ref_max_len, revcomp, (const uint32_t *)qry_packed, qry_lens, qry_max_len,
+                     npairs, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost, nullptr, ATR_PAIRS_AUTO, (uint32_t *)out);
+}
+EMU_TWIN(locate_pairs_batch);
+
+int emu_locate_pairs_full_batch(const uint8_t *ref_packed, const int32_t *ref_lens, int ref_max_len, int revcomp,
+    const uint8_t *qry_packed, const int32_t *qry_lens, int qry_max_len, int64_t npairs, double e, int flags,
+    int wildcard_ref, int wildcard_query, int min_overlap, int indel_cost, atr_result *out, void *) {
+    return pairs_batch((const uint32_t *)ref_packed, ref_lens, ref_max_len, revcomp, (const uint32_t *)qry_packed, qry_lens, qry_max_len,
+                     npairs, e, flags, wildcard_ref, wildcard_query, min_overlap, indel_cost, nullptr, ATR_PAIRS_FULL, (uint32_t *)out);
+}
+EMU_TWIN(locate_pairs_full_batch);
 
 }  // extern "C"

@@ -4,10 +4,11 @@
 // counts into a table of the round's length and rebases it, as the kernel's flush does.  A harness for the CPU tier,
 // not parity evidence for the kernels.
 #include <stdint.h>
+#include <string.h>
 
 #include <vector>
 
-#include "atropos_hip.h"
+#include "emu_abi.hpp"
 #include "fastq_core.hpp"
 #include "report_core.hpp"
 
@@ -24,22 +25,38 @@ int emu_report_create(int n_adapters, int max_read_len, int max_errors, void **o
     *out = new RepLayout(L);
     return 0;
 }
+EMU_TWIN(report_create);
 
 void emu_report_destroy(void *h) { delete (RepLayout *)h; }
+EMU_TWIN(report_destroy);
 
 int64_t emu_report_counters(const void *h) { return h ? rep_words(*(const RepLayout *)h) : -1; }
+EMU_TWIN(report_counters);
 
-int emu_report_intervals(const void *h, const FastqRecord *recs, const int32_t *b0, const int32_t *e0, const int32_t *b1,
-                         const int32_t *e1, int64_t n, int mode, int front, int back, int slot, int64_t *counters) {
+int emu_report_read(const void *h, const void *counters, int64_t *out, void *) {
+    if (!h) return -1;
+    memcpy(out, counters, 8 * (size_t)emu_report_counters(h));
+    return 0;
+}
+EMU_TWIN(report_read);
+
+int emu_report_intervals(const void *h, const atr_fastq_record *records, const int32_t *b0, const int32_t *e0, const int32_t *b1,
+                         const int32_t *e1, int64_t n, int mode, int front, int back, int slot, void *d_counters, void *) {
+    const FastqRecord *recs = (const FastqRecord *)records;
+    int64_t *counters = (int64_t *)d_counters;
     if (!h || n < 0 || mode < REP_SUBSEQ || mode > REP_NEND || front < 0 || back < 0 || slot < 0 || slot >= REP_SLOTS) return -1;
     for (int64_t i = 0; i < n; ++i)
         counters[REP_TRIM + slot] += rep_trimmed_bases(mode, b0[i], e0[i], b1[i], e1[i], front, back, (int)recs[i].seq_len);
     return 0;
 }
+EMU_TWIN(report_intervals);
 
-int emu_report_adapters(const void *h, const uint8_t *bytes, const FastqRecord *recs, const uint8_t *took, const int16_t *best,
-                        const int64_t *which, const uint8_t *front, int default_front, const int32_t *begin,
-                        const int32_t *end, int64_t n, int longest, int weight, int variant, int64_t *counters) {
+int emu_report_adapters(const void *h, const uint8_t *bytes, const atr_fastq_record *records, const uint8_t *took,
+                        const int16_t *best, const int64_t *which, const uint8_t *front, int default_front,
+                        const int32_t *begin, const int32_t *end, int64_t n, int longest, int weight, int variant,
+                        void *d_counters, void *) {
+    const FastqRecord *recs = (const FastqRecord *)records;
+    int64_t *counters = (int64_t *)d_counters;
     if (!h || n < 0 || longest < 0 || weight < 1 || weight > 2 || variant < 0 || variant > 2) return -1;
     const RepLayout G = *(const RepLayout *)h;
     if (longest > G.max_len) return -2;
@@ -70,9 +87,12 @@ int emu_report_adapters(const void *h, const uint8_t *bytes, const FastqRecord *
         if (lds[w]) table[rep_rebase_word(S, G, (int64_t)w)] += lds[w];
     return 0;
 }
+EMU_TWIN(report_adapters);
 
-int emu_report_outputs(const void *h, const FastqRecord *recs, const int32_t *begin, const int32_t *end, const uint8_t *matched,
-                       const uint8_t *dest, int64_t n, int64_t *counters) {
+int emu_report_outputs(const void *h, const atr_fastq_record *records, const int32_t *begin, const int32_t *end,
+                       const uint8_t *matched, const uint8_t *dest, int64_t n, void *d_counters, void *) {
+    const FastqRecord *recs = (const FastqRecord *)records;
+    int64_t *counters = (int64_t *)d_counters;
     if (!h || n < 0) return -1;
     for (int64_t i = 0; i < n; ++i) {
         const int d = dest[i] < REP_DESTS ? dest[i] : REP_DESTS - 1;
@@ -84,5 +104,6 @@ int emu_report_outputs(const void *h, const FastqRecord *recs, const int32_t *be
     }
     return 0;
 }
+EMU_TWIN(report_outputs);
 
 }  // extern "C"

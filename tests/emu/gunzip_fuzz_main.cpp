@@ -14,7 +14,8 @@
 #include <string.h>
 
 extern "C" int emu_gunzip_members(const uint8_t *stream, int64_t n_stream, const int64_t *member_at, const int64_t *text_at,
-                                  int64_t n_members, uint8_t *text, int64_t text_capacity, int32_t *status, int32_t *bad);
+                                  int64_t n_members, uint8_t *text, int64_t text_capacity, int32_t *status, int32_t *bad,
+                                  void *);
 
 static uint32_t get32(FILE *f) {
     uint8_t b[4];
@@ -44,7 +45,7 @@ int main(int argc, char **argv) {
         memset(text, 0xa5, room ? room : 1);
         const int64_t member_at[2] = {0, (int64_t)size}, text_at[2] = {0, (int64_t)isize};
         int32_t status = -1, bad = -1;
-        const int rc = emu_gunzip_members(member, size, member_at, text_at, size >= 26 ? 1 : 0, text, room, &status, &bad);
+        const int rc = emu_gunzip_members(member, size, member_at, text_at, size >= 26 ? 1 : 0, text, room, &status, &bad, nullptr);
         if (size < 26) status = 1;                          // (fewer bytes than a member has: no member to run)
         else if (rc != 0 || bad != (status != 0)) { fprintf(stderr, "gunzip_fuzz: case %u: rc %d, bad %d, status %d\n", i, rc, bad, status); return 3; }
         put32(out, (uint32_t)status);

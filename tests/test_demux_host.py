@@ -8,6 +8,7 @@ from atropos_amd.fastq import FastqBatch
 from atropos_amd.trim import TrimPipeline, pipeline_from_args
 
 from . import _demux_common as D
+from .emu.backend import EmuBackend
 
 TRUSEQ = "AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
 SHORT = "ACGTTGCAAC"
@@ -15,7 +16,7 @@ SHORT = "ACGTTGCAAC"
 
 @pytest.fixture()
 def demux_backend():
-    prev = _lib.set_backend(D.DemuxEmuBackend(), _test_double=True)
+    prev = _lib.set_backend(EmuBackend(), _test_double=True)
     yield _lib.get_backend()
     _lib.set_backend(prev, _test_double=True)
 

@@ -152,7 +152,8 @@ def test_ratio(hip_backend, kind):
 
 def test_same_bytes_as_the_twin(hip_backend):
     """The kernels and their CPU twin run one source (deflate_core.hpp): the streams are identical."""
-    twin = G.GzipEmuBackend()
+    from .emu.backend import EmuBackend
+    twin = EmuBackend()
     inputs = [G.ratio_fixture("binned")[:3 * G.BLOCK + 99], G.CONTENTS["fibonacci"](G.BLOCK + 5), G.CONTENTS["random"](700)]
     for content, edge in (("cl_limit", 511), ("every_symbol", 16385), ("segment_cut", 4097), ("tail_match", 513),
                           ("tail_match_far", 20480), ("window_edge", 32769 + 600)):

@@ -20,6 +20,30 @@ def test_native_library_is_loaded(hip_backend):
     assert _lib.get_backend() is hip_backend
 
 
+def test_calls_on_a_worker_stream_equal_the_default_stream(hip_backend):
+    """pack_reads + locate_batch inside ``worker_context()`` (a stream of its own) give the records of the same calls
+    on the default stream: 130 reads of 40 bases, three tiles with a ragged last one, every path that takes them."""
+    from atropos_amd import synth
+    be = hip_backend
+    reads = synth.single_end(0, 130, 40, synth.TRUSEQ_34, synth.SEEDS["C2"], device=be.device)
+    h = be.aligner_create(synth.TRUSEQ_34.encode(), 0.1, 14, False, False, 3, 1)
+    table = be.aligner_query_table(h)[1]
+
+    def records(path):
+        packed = be.pack_reads(reads, None, 40, table)
+        return be.locate_batch(h, packed, None, 130, 40, path=path)
+    try:
+        for path in ("auto", "full", "filtered", "wave"):
+            want = records(path).cpu()
+            with be.worker_context() as stream:
+                assert torch.cuda.current_stream(be.device) == stream != torch.cuda.default_stream(be.device)
+                got = records(path)
+            assert torch.equal(got.cpu(), want), path
+            assert int((want[:, 1] >= 0).sum()) > 10
+    finally:
+        be.aligner_destroy(h)
+
+
 def test_golden_locate(hip_backend):
     from atropos_amd import _lib
     from atropos_amd.align import Aligner

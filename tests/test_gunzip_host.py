@@ -16,16 +16,12 @@ from atropos_amd import _lib
 
 from . import _gunzip_common as U
 from . import _gzip_common as G
-from ._detect_common import DetectEmuBackend
-
-
-class _Backend(U.GunzipEmuBackend, DetectEmuBackend):
-    """The twins of the inflater, of the compressor and of the detect kernels on one test backend."""
+from .emu.backend import EmuBackend
 
 
 @pytest.fixture(scope="module")
 def twin():
-    return _Backend()
+    return EmuBackend()
 
 
 @pytest.fixture()
@@ -191,12 +187,11 @@ def test_scan(twin):
 def test_abi_errors(twin, which):
     """The refusals come before any pointer is looked at (the library's too: no device is needed for them)."""
     if which == "twin":
-        scan = twin.gunz.emu_bgzf_scan
-        members = lambda *a: twin.gunz.emu_gunzip_members(*a)
+        scan, gunzip = twin._symbol("atr_bgzf_scan"), twin._symbol("atr_gunzip_members")
     else:
         lib = _lib.load_library()
-        scan = lib.atr_bgzf_scan
-        members = lambda *a: lib.atr_gunzip_members(*(a + (None,)))
+        scan, gunzip = lib.atr_bgzf_scan, lib.atr_gunzip_members
+    members = lambda *a: gunzip(*(a + (None,)))
     assert members(None, -1, None, None, 0, None, 0, None, None) == -1
     assert members(None, 100, None, None, -1, None, 0, None, None) == -1
     assert members(None, 100, None, None, 1, None, -1, None, None) == -1

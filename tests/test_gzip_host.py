@@ -14,11 +14,12 @@ from atropos_amd import _lib, fastq
 from atropos_amd.trim import pipeline_from_args
 
 from . import _gzip_common as G
+from .emu.backend import EmuBackend
 
 
 @pytest.fixture(scope="module")
 def twin():
-    return G.GzipEmuBackend()
+    return EmuBackend()
 
 
 @pytest.fixture()
@@ -100,7 +101,7 @@ def test_build_lengths_fuzz(twin, nmax, maxbits, count):
     for freqs in _fuzz_histograms(np.random.default_rng(nmax), nmax, count):
         if sum(freqs) >= 1 << 32:
             continue
-        lengths = G.twin_build_lengths(twin.gz, freqs, maxbits)
+        lengths = G.twin_build_lengths(freqs, maxbits)
         ratio = G.check_code(freqs, lengths, maxbits, "fuzz %r" % (freqs[:8],))
         if ratio is not None:
             bound += 1
@@ -119,17 +120,18 @@ def test_deterministic_and_concatenation(twin):
 
 def test_abi_errors(twin):
     """The refusals come before any pointer is looked at."""
-    lib = twin.gz
-    assert lib.emu_gzip_bound(-1) == -1 and lib.emu_gzip_work_bytes(-1) == 0
-    assert lib.emu_gzip_bound(0) == 0 and lib.emu_gzip_bound(G.BLOCK + 1) == G.BLOCK + 1 + 2 * 31
-    assert lib.emu_gzip_blocks(None, -1, None, 0, None, None, None) == -1
-    assert lib.emu_gzip_blocks(None, 100, None, lib.emu_gzip_bound(100) - 1, None, None, None) == -1
-    assert lib.emu_gzip_blocks(None, 100, None, -5, None, None, None) == -1
-    assert lib.emu_gzip_blocks(None, 1 << 32, None, lib.emu_gzip_bound(1 << 32), None, None, None) == -2
-    assert lib.emu_gzip_blocks(None, 100, None, lib.emu_gzip_bound(100), None, None, None) == -1
+    bound, work_bytes = twin._symbol("atr_gzip_bound"), twin._symbol("atr_gzip_work_bytes")
+    blocks = lambda *a: twin._symbol("atr_gzip_blocks")(*(a + (None,)))         # (the stream)
+    assert bound(-1) == -1 and work_bytes(-1) == 0
+    assert bound(0) == 0 and bound(G.BLOCK + 1) == G.BLOCK + 1 + 2 * 31
+    assert blocks(None, -1, None, 0, None, None, None) == -1
+    assert blocks(None, 100, None, bound(100) - 1, None, None, None) == -1
+    assert blocks(None, 100, None, -5, None, None, None) == -1
+    assert blocks(None, 1 << 32, None, bound(1 << 32), None, None, None) == -2
+    assert blocks(None, 100, None, bound(100), None, None, None) == -1
     buf = (16 * b"\xaa" + 12 * b"\xaa")
     raw = torch.frombuffer(bytearray(buf), dtype=torch.uint8)
-    assert lib.emu_gzip_eof(raw.data_ptr()) == 28
+    assert twin._symbol("atr_gzip_eof")(raw.data_ptr()) == 28
     assert bytes(raw.numpy().tobytes()) == G.EOF == _lib.GZIP_EOF
     assert gzip.decompress(G.EOF) == b""
 

@@ -7,13 +7,14 @@ from atropos_amd import _lib
 from atropos_amd.trim import pipeline_from_args
 
 from . import _report_common as R
+from .emu.backend import EmuBackend
 
 TRUSEQ = "AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
 
 
 @pytest.fixture()
 def report_backend():
-    prev = _lib.set_backend(R.ReportEmuBackend(), _test_double=True)
+    prev = _lib.set_backend(EmuBackend(), _test_double=True)
     yield _lib.get_backend()
     _lib.set_backend(prev, _test_double=True)
 
