@@ -188,6 +188,13 @@ PROTOTYPES = {
     "atr_fastq_emit_work_bytes": (C.c_size_t, [C.c_int64]),
     "atr_fastq_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
+    "atr_fastq_emit_pairs_work_bytes": (C.c_size_t, [C.c_int64]),
+    "atr_fastq_emit_pairs": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 3 + [STREAM]),
+    "atr_overwrite_work_bytes": (C.c_size_t, [C.c_int64]),
+    "atr_overwrite_plan_batch": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
+                                 + [STREAM]),
+    "atr_overwrite_apply_batch": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_char_p,
+                                                                                            C.c_void_p, STREAM]),
     "atr_fastq_emit_grouped_work_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "atr_fastq_emit_grouped": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 4 + [STREAM]),
     "atr_demux_groups": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64, C.c_void_p, STREAM]),
@@ -845,7 +852,85 @@ class AbiCalls(object):
         return out
 
 
-class HipBackend(AbiCalls):
+class StatsCalls(object):
+    """The wrappers of the read-statistics entry points (atr_read_stats_*), written against ``_call`` / ``_host`` like
+    ``AbiCalls``' methods.  A mixin of its own: the CPU test-suite serves these entry points from a twin library of
+    their own (tests/emu/emu_stats.cpp)."""
+
+    def read_stats_words(self, max_len):
+        """uint64 words of a statistics block for reads of up to ``max_len`` bases."""
+        return self._host("atr_read_stats_bytes", int(max_len)) // 8
+
+    def read_stats_clear(self, block, max_len):
+        self._call("atr_read_stats_clear", _ptr(block), int(max_len))
+
+    def read_stats_batch(self, block, max_len, longest, quality_base, data, records, begin=None, end=None, ubegin=None,
+                         uend=None, dest=None, which=0, index_base=0):
+        """Adds the records (their kept intervals, masks and destination filter as atr_fastq_emit) into ``block``;
+        record r is read ``index_base + r`` of the stream."""
+        self._call("atr_read_stats_batch", _ptr(block), int(max_len), int(longest), int(quality_base), _ptr(data),
+                   _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(dest), int(which), records.shape[0],
+                   int(index_base))
+
+    def read_stats_merge(self, dst, dst_max_len, src, src_max_len, index_offset=0):
+        self._call("atr_read_stats_merge", _ptr(dst), int(dst_max_len), _ptr(src), int(src_max_len), int(index_offset))
+
+
+class PairTextCalls(object):
+    """The wrappers of the paired-text entry points (interleaved output), written against ``_call`` / ``_host`` /
+    ``empty`` like ``AbiCalls``' methods.  A mixin of its own: the CPU test-suite serves these entry points from a
+    twin library of their own (tests/emu/emu_pairtext.cpp)."""
+
+    def fastq_emit_pairs(self, batch1, begin1, end1, ubegin1, uend1, batch2, begin2, end2, ubegin2, uend2, dest, which):
+        """Formatted FASTQ text (uint8 device tensor) of the pairs with dest == which (dest None: all of them): read
+        1's record, then read 2's, pair after pair (atr_fastq_emit_pairs).  ``batch1`` / ``batch2``: anything with
+        ``data`` and ``records`` (a FastqBatch); the two may share one ``data`` tensor (interleaved input)."""
+        n = batch1.records.shape[0]
+        if batch2.records.shape[0] != n:
+            raise ValueError("fastq_emit_pairs: the two record arrays hold different numbers of records")
+        offsets = self.empty((n + 1,), torch.int64)
+        work = self.empty((max(self._host("atr_fastq_emit_pairs_work_bytes", n), 16),), torch.uint8)
+        nbytes = batch1.data.numel()
+        if batch2.data.data_ptr() != batch1.data.data_ptr():
+            nbytes += batch2.data.numel()
+        hint = int(nbytes // max(n, 1))
+        args = (_ptr(batch1.data), _ptr(batch1.records), _ptr(begin1), _ptr(end1), _ptr(ubegin1), _ptr(uend1),
+                _ptr(batch2.data), _ptr(batch2.records), _ptr(begin2), _ptr(end2), _ptr(ubegin2), _ptr(uend2),
+                _ptr(dest), which, n, hint, _ptr(offsets), _ptr(work))
+        self._call("atr_fastq_emit_pairs", *args, None)
+        total = int(offsets[n].item())
+        out = self.empty((max(total, 1),), torch.uint8)
+        if total:
+            self._call("atr_fastq_emit_pairs", *args, _ptr(out))
+        return out[:total]
+
+
+    def overwrite_plan(self, batch1, begin1, end1, batch2, begin2, end2, lowq, highq, window, quality_base):
+        """OverwriteRead's decisions over the kept intervals (atr_overwrite_plan_batch): (which uint8 [n] -- 0 none, 1
+        read 1 overwritten, 2 read 2 --, grow1, grow2 int64 [n + 1]: where every clone goes in the tail of the chunk of
+        read 1 / read 2, [n] the bytes that tail needs)."""
+        n = batch1.records.shape[0]
+        which = self.empty((n,), torch.uint8)
+        grow1, grow2 = self.empty((n + 1,), torch.int64), self.empty((n + 1,), torch.int64)
+        work = self.empty((max(self._host("atr_overwrite_work_bytes", n), 16),), torch.uint8)
+        self._call("atr_overwrite_plan_batch", _ptr(batch1.data), _ptr(batch1.records), _ptr(begin1), _ptr(end1),
+                   _ptr(batch2.data), _ptr(batch2.records), _ptr(begin2), _ptr(end2), n, int(lowq), int(highq), int(window),
+                   int(quality_base), _ptr(which), _ptr(grow1), _ptr(grow2), _ptr(work))
+        return which, grow1, grow2
+
+    def overwrite_apply(self, data1, records1, begin1, end1, data2, records2, begin2, end2, which, grow1, grow2, tail1, tail2,
+                        comp):
+        """Writes the clones into the grown chunks and re-points ``records`` / ``begin`` / ``end`` of the overwritten
+        reads IN PLACE (atr_overwrite_apply_batch); returns the error word."""
+        n = records1.shape[0]
+        err = self.empty((1,), torch.int64)
+        self._call("atr_overwrite_apply_batch", _ptr(data1), _ptr(records1), _ptr(begin1), _ptr(end1), _ptr(data2),
+                   _ptr(records2), _ptr(begin2), _ptr(end2), n, _ptr(which), _ptr(grow1), _ptr(grow2), int(tail1), int(tail2),
+                   comp, _ptr(err))
+        return int(err.item())
+
+
+class HipBackend(AbiCalls, PairTextCalls, StatsCalls):
     """Thin object view of the C ABI; all buffers are torch tensors on one GPU.  The calls the CPU test-suite's stand-in
     serves as well are ``AbiCalls``'; here are the plumbing under them and the device-only calls."""
 
@@ -1090,25 +1175,6 @@ class HipBackend(AbiCalls):
             self._call("atr_linked_group_match", h, _ptr(g.grouped), _ptr(g.glens), g.info, g.max_len, _ptr(g.slot_of),
                        _ptr(g.which), g.nreads, _ptr(slab), _ptr(back), _ptr(g.work))
         return slab, back
-
-    # -- read statistics (atr_read_stats_*) ---------------------------------------------------------------------
-    def read_stats_words(self, max_len):
-        """uint64 words of a statistics block for reads of up to ``max_len`` bases."""
-        return self._host("atr_read_stats_bytes", int(max_len)) // 8
-
-    def read_stats_clear(self, block, max_len):
-        self._call("atr_read_stats_clear", _ptr(block), int(max_len))
-
-    def read_stats_batch(self, block, max_len, longest, quality_base, data, records, begin=None, end=None, ubegin=None,
-                         uend=None, dest=None, which=0, index_base=0):
-        """Adds the records (their kept intervals, masks and destination filter as atr_fastq_emit) into ``block``;
-        record r is read ``index_base + r`` of the stream."""
-        self._call("atr_read_stats_batch", _ptr(block), int(max_len), int(longest), int(quality_base), _ptr(data),
-                   _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(dest), int(which), records.shape[0],
-                   int(index_base))
-
-    def read_stats_merge(self, dst, dst_max_len, src, src_max_len, index_offset=0):
-        self._call("atr_read_stats_merge", _ptr(dst), int(dst_max_len), _ptr(src), int(src_max_len), int(index_offset))
 
 
 _backend = None

@@ -459,7 +459,7 @@ class PairedDetector(object):
 
 
 # ---------------------------------------------------------------------------------------------- file drivers
-def _detect_paths(paths, detector_class, known_contaminants, max_reads, chunk_bytes, kwargs):
+def _detect_paths(paths, detector_class, known_contaminants, max_reads, chunk_bytes, kwargs, interleaved=False):
     """The chunks of ``fastq.read_chunks`` into a detector until ``max_reads`` records went in; its summary."""
     report = {k: kwargs.pop(k) for k in ("min_len", "min_complexity", "min_match_frac", "limit") if k in kwargs}
     device_gunzip = kwargs.pop("device_gunzip", False)        # (BGZF .gz input inflated on the GPU: fastq.ChunkedFastqReader)
@@ -467,7 +467,7 @@ def _detect_paths(paths, detector_class, known_contaminants, max_reads, chunk_by
     det = detector_class(known_contaminants, **kwargs)
     try:
         left = max_reads
-        for batches in read_chunks(paths, chunk_bytes, device_gunzip=device_gunzip):
+        for batches in read_chunks(paths, chunk_bytes, device_gunzip=device_gunzip, interleaved=interleaved):
             if left is not None:
                 batches = [b.head(left)[0] for b in batches]
                 left -= len(batches[0])
@@ -488,8 +488,10 @@ def detect_file(path, known_contaminants, max_reads=10000, chunk_bytes=64 << 20,
 
 
 def detect_files(path1, path2, known_contaminants, max_reads=10000, chunk_bytes=64 << 20, **kwargs):
-    """The same for paired files: ``matches`` is a 2-tuple of lists, one per read."""
-    return _detect_paths([path1, path2], PairedDetector, known_contaminants, max_reads, chunk_bytes, kwargs)
+    """The same for paired files: ``matches`` is a 2-tuple of lists, one per read.  ``path2=None``: ``path1`` is an
+    interleaved file (the reference's ``-l``), as in ``trim_files``; ``max_reads`` counts pairs either way."""
+    paths = [path1] if path2 is None else [path1, path2]
+    return _detect_paths(paths, PairedDetector, known_contaminants, max_reads, chunk_bytes, kwargs, interleaved=path2 is None)
 
 
 def detect_from_args(argv, paired=False):

@@ -45,16 +45,28 @@ class FastqBatch(object):
     the reference reads its input.
     """
 
-    def __init__(self, data, nbytes, records, backend, line_ends=None):
+    def __init__(self, data, nbytes, records, backend, line_ends=None, stride=1):
         self.data, self.nbytes, self.records, self.backend = data, nbytes, records, backend
         self.line_ends = line_ends
+        # records of the chunk per record of this batch: 2 for the mates of an interleaved chunk (``mates``), whose
+        # ``records`` are every other descriptor of the chunk while ``line_ends`` are the chunk's
+        self.stride = int(stride)
 
     def head(self, nrec):
         """The first ``nrec`` records as a batch of their own, and the number of bytes of text
-        they occupy (paired files are consumed in lock step: the shorter chunk decides)."""
+        they occupy (paired files are consumed in lock step: the shorter chunk decides).  For a mate of an interleaved
+        chunk that is the text of the first ``nrec`` PAIRS."""
         nrec = min(int(nrec), len(self))
-        consumed = int(self.line_ends[4 * nrec - 1].item()) + 1 if nrec else 0
-        return FastqBatch(self.data, self.nbytes, self.records[:nrec], self.backend, self.line_ends), consumed
+        consumed = int(self.line_ends[4 * nrec * self.stride - 1].item()) + 1 if nrec else 0
+        return FastqBatch(self.data, self.nbytes, self.records[:nrec], self.backend, self.line_ends, self.stride), consumed
+
+    def mates(self):
+        """The even and the odd records of an interleaved chunk (an even number of records) as two batches, read 1 and
+        read 2 of the pairs: strided views of the descriptors made contiguous, over the one ``data`` tensor."""
+        if len(self) % 2 or self.stride != 1:
+            raise ValueError("mates(): a whole chunk with an even number of records is needed")
+        return [FastqBatch(self.data, self.nbytes, self.records[k::2].contiguous(), self.backend, self.line_ends, 2)
+                for k in (0, 1)]
 
     def __len__(self):
         return self.records.shape[0]
@@ -711,7 +723,7 @@ class ChunkedFastqReader(object):
         self.buf = []
 
 
-def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, device_gunzip=False):
+def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, device_gunzip=False, interleaved=False):
     """THE chunk loop of every file driver (trim, qc, error rate, detect, a rank's shard): yields a list of
     FastqBatch, one per path, chunk after chunk of whole records.  Several paths are read in lock step: every
     batch of a list holds the same number of records (the file whose chunk holds fewer decides, the surplus of the
@@ -721,15 +733,37 @@ def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, 
     consumer works.  A chunk may hold no whole record; it is yielded all the same.  The readers are closed when the
     loop ends, however it ends -- a consumer that has enough just leaves its ``for`` loop.  ``byte_ranges``: one
     (lo, hi) or None per path (``ChunkedFastqReader``).  ``device_gunzip``: BGZF ``.gz`` input is inflated on the GPU
-    (``ChunkedFastqReader``); every other input is read as without it."""
+    (``ChunkedFastqReader``); every other input is read as without it.
+
+    ``interleaved``: the one path holds pairs, read 1 and read 2 in turn (the reference's ``-l``): every list holds TWO
+    batches, the even and the odd records of the chunk (``FastqBatch.mates``: one ``data`` tensor).  A chunk with an
+    odd number of records hands out all but the last, which is carried over like the surplus of a two-file run; an
+    odd number of records in the whole file is the reference's FormatError (io/seqio.py:499-502).  The names of the
+    two reads are not compared -- the two-file readers do not compare them either.  With ``byte_ranges`` it is a
+    ValueError: a range may begin at a read 2."""
     mismatch = "the two input files hold different numbers of records"
+    if interleaved:
+        if len(paths) != 1:
+            raise ValueError("interleaved input is one file")
+        if byte_ranges is not None and any(r is not None for r in byte_ranges):
+            raise ValueError("byte ranges of an interleaved file are not provided (a range may begin at a read 2)")
     readers = []
     try:
         for path, byte_range in zip(paths, byte_ranges or [None] * len(paths)):
             readers.append(ChunkedFastqReader(path, chunk_bytes, backend, clock, byte_range, device_gunzip))
         while True:
             batches = [r.next_batch() for r in readers]
-            if len(readers) == 1:
+            if interleaved:
+                reader, batch = readers[0], batches[0]
+                if len(batch) % 2:
+                    if reader.final:
+                        raise FormatError("Interleaved input file incomplete: Last record has no partner.")
+                    batch, consumed = batch.head(len(batch) - 1)
+                    done = [reader.advance(consumed)]
+                else:
+                    done = [reader.advance()]
+                batches = batch.mates()
+            elif len(readers) == 1:
                 done = [readers[0].advance()]                 # (all whole records: no head(), no device sync)
             else:
                 nrec = min(len(b) for b in batches)

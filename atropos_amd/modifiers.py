@@ -224,6 +224,37 @@ def _mirrored(match, read_len):
     return twin
 
 
+class OverwriteRead(ReadPairModifier):
+    """``-w / --overwrite-low-quality LOWQ,HIGHQ,WINDOW`` on the per-read object path (commands/trim/modifiers.py:511-563):
+    if the mean quality of the first ``window_size`` bases of one read is below ``worse_read_min_quality`` and that of
+    the other read is at least ``better_read_min_quality``, the worse read is replaced by the reverse complement of
+    the better one (``Read.reverse_complement``: its name, its bases complemented in reverse order, its qualities
+    reversed), whose ``corrected`` flag is set first.  Pairs with a read shorter than the window are left alone.
+    Host code over two read objects; the device pipelines have no stage for it yet (op-order letter ``W``)."""
+
+    def __init__(self, worse_read_min_quality, better_read_min_quality, window_size, base=33, summary_fn=None):
+        self.worse_read_min_quality = worse_read_min_quality
+        self.better_read_min_quality = better_read_min_quality
+        self.window_size = window_size
+        self.base = base
+        self.summary_fn = summary_fn or (lambda values: float(sum(values)) / len(values))       # util.mean
+
+    def __call__(self, read1, read2):
+        if len(read1) < self.window_size or len(read2) < self.window_size:
+            return (read1, read2)
+        if not (read1.qualities and read2.qualities):
+            raise ValueError("OverwriteRead modifier does not work with reads lacking base qualities.")
+        summ1, summ2 = (self.summary_fn([ord(q) - self.base for q in read.qualities[:self.window_size]])
+                        for read in (read1, read2))
+        if summ1 < self.worse_read_min_quality and summ2 >= self.better_read_min_quality:
+            read2.corrected = 1
+            read1 = read2.reverse_complement()
+        elif summ2 < self.worse_read_min_quality and summ1 >= self.better_read_min_quality:
+            read1.corrected = 1
+            read2 = read1.reverse_complement()
+        return (read1, read2)
+
+
 class InsertAdapterCutter(ReadPairModifier, ErrorCorrectorMixin):
     """AdapterCutter that uses InsertAligner to first try to identify the insert overlap
     before falling back to semi-global adapter alignment (reference modifiers.py:359-509).

@@ -41,6 +41,24 @@ class Read(object):
             part.qualities = self.qualities[key]
         return part
 
+    def reverse_complement(self):
+        """A copy of this read with the sequence reverse-complemented (``util.BASE_COMPLEMENTS``: a base without a
+        complement is a ``KeyError``) and the qualities reversed; name, name2, ``original_length``, ``clipped``,
+        ``insert_overlap``, ``merged`` and ``corrected`` are the read's own, ``match_info`` and ``match`` copies of
+        them (Sequence.reverse_complement, io/_seqio.pyx:88-120)."""
+        import copy
+        from .util import reverse_complement
+        flipped = Read(self.name, reverse_complement(self.sequence),
+                       "".join(reversed(self.qualities)) if self.qualities else None, self.name2, self.original_length,
+                       list(self.clipped), match_info=[copy.copy(m) for m in self.match_info] if self.match_info else None,
+                       insert_overlap=self.insert_overlap, merged=self.merged, corrected=self.corrected)
+        if type(self) is not Read:
+            flipped.__class__ = type(self)
+        if self.match:
+            flipped.match = self.match.copy()
+            flipped.match.read = flipped
+        return flipped
+
     def _key(self):
         return tuple(getattr(self, slot) for slot in ("name", "sequence", "qualities"))
 

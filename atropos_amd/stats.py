@@ -313,20 +313,25 @@ def qc_file(path, chunk_bytes=64 << 20, quality_base=33, qualities=True, device_
     return {"pre": {0: st.summarize()}}
 
 
-def qc_files(path1, path2, chunk_bytes=64 << 20, quality_base=33, qualities=True, device_gunzip=False):
-    """``atropos qc`` of paired files: {"pre": {0: {"read1": ..., "read2": ...}}}."""
+def qc_files(path1, path2=None, chunk_bytes=64 << 20, quality_base=33, qualities=True, device_gunzip=False):
+    """``atropos qc`` of paired files: {"pre": {0: {"read1": ..., "read2": ...}}}.  ``path2=None``: ``path1`` is an
+    interleaved file (the reference's ``-l``; ``fastq.read_chunks(interleaved=True)``)."""
     st = PairedEndReadStatistics(qualities=qualities, quality_base=quality_base)
-    for batches in read_chunks([path1, path2], chunk_bytes, device_gunzip=device_gunzip):
+    paths = [path1] if path2 is None else [path1, path2]
+    for batches in read_chunks(paths, chunk_bytes, device_gunzip=device_gunzip, interleaved=path2 is None):
         st.collect_batch(*batches)
     return {"pre": {0: st.summarize()}}
 
 
-def error_rate_file(path, path2=None, max_bases=None, chunk_bytes=64 << 20, device_gunzip=False):
+def error_rate_file(path, path2=None, max_bases=None, chunk_bytes=64 << 20, device_gunzip=False, interleaved=False):
     """``atropos error -a quality``: (estimates, total_lens), one entry per input file, as
-    BaseQualityErrorEstimator / PairedErrorEstimator put them in the summary."""
+    BaseQualityErrorEstimator / PairedErrorEstimator put them in the summary.  ``interleaved``: ``path`` alone holds
+    the pairs (the reference's ``-l``); one entry per read, as for two files."""
+    if interleaved and path2 is not None:
+        raise ValueError("interleaved input is one file")
     paths = [path] if path2 is None else [path, path2]
-    sts = [ReadStatistics(qualities=True) for _ in paths]
-    for batches in read_chunks(paths, chunk_bytes, device_gunzip=device_gunzip):
+    sts = [ReadStatistics(qualities=True) for _ in range(2 if interleaved else len(paths))]
+    for batches in read_chunks(paths, chunk_bytes, device_gunzip=device_gunzip, interleaved=interleaved):
         for st, batch in zip(sts, batches):
             st.collect_batch(batch)
     res = [s.error_rate(max_bases) for s in sts]

@@ -20,6 +20,8 @@ Stages, in the order the reference's ``op_order`` (default "CGQAW") and the fixe
   -  MergeOverlapping (-R, paired)  -> atr_locate_pairs_batch + atr_merge_plan_batch + atr_merge_emit_batch
   -  ZeroCapper (-z) and the read-name modifiers (length tag, suffix removal, prefix / suffix)
   -  FastqFormat                    -> atr_fastq_emit
+  W  OverwriteRead (-w, paired)     -> atr_overwrite_plan_batch + atr_overwrite_apply_batch
+  -  InterleavedFormatter (-L)      -> atr_fastq_emit_pairs (interleaved input, -l, is fastq.read_chunks' business)
   -  Formatters (``{name}`` in the output path: one file per adapter name)
                                     -> atr_demux_groups + atr_fastq_emit_grouped
 
@@ -260,15 +262,23 @@ class _Mate(object):
         self.last_which = (torch.zeros((n,), dtype=torch.int64, device=self.begin.device)
                            if ("{name}" in pipe.prefix or "{name}" in pipe.suffix or pipe.demultiplex) else None)
         self.unmasked = None                                  # a copy of the chunk before the mask / the zero cap
+        # OverwriteRead: (the reads that are clones of their mates, the mate's adapters) -- a clone carries the mate's
+        # match, so `last_which` of those reads indexes the OTHER read's adapter list ({name} in --prefix / --suffix)
+        self.foreign = None
 
 
-def _run_stages(pipes, mates, insert_stage=None):
+def _run_stages(pipes, mates, insert_stage=None, overwrite_stage=None):
     """The op-order stages, ``pipes[k]`` over ``mates[k]`` (one read, or the two reads of the pairs).  The A stage is
     ``insert_stage()`` if given (the paired insert aligner), else the adapter stage of every pipe that has adapters;
-    returns what the last ``insert_stage()`` returned."""
+    the W stage is ``overwrite_stage()`` if given (OverwriteRead, pairs only); returns what the last
+    ``insert_stage()`` returned."""
     op_order, action = pipes[0].op_order, pipes[0].action
     found = None
     for op in op_order:
+        if op == "W":
+            if overwrite_stage is not None:
+                overwrite_stage()
+            continue
         if op != "A":
             for pipe, m in zip(pipes, mates):
                 pipe._simple_stage(op, m)
@@ -290,9 +300,13 @@ def _run_stages(pipes, mates, insert_stage=None):
 
 def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out=None, byte_ranges=None,
                  device_gzip=False, device_gunzip=False):
-    """What ``TrimPipeline.trim_file`` (one input), ``PairedTrimPipeline.trim_files`` (two inputs in lock step) and
-    ``shard.sharded_trim_file`` (``byte_ranges``: a rank's part of the input) do with every chunk of
-    ``fastq.read_chunks``; returns the destination counts."""
+    """What ``TrimPipeline.trim_file`` (one input), ``PairedTrimPipeline.trim_files`` (two inputs in lock step, or one
+    interleaved input) and ``shard.sharded_trim_file`` (``byte_ranges``: a rank's part of the input) do with every
+    chunk of ``fastq.read_chunks``; returns the destination counts.  A paired pipeline with ONE input path reads it as
+    an interleaved file, with ONE output path it writes the pairs interleaved (``atr_fastq_emit_pairs``)."""
+    if _is_paired(pipe) and len(paths_out) == 1 and pipe.outputs:
+        raise NotImplementedError("interleaved output with --too-short-output / --too-long-output / --untrimmed-output "
+                                  "(the reference interleaves those files as well)")
     if device_gzip:
         # the main outputs compressed on the device (fastq.DeviceGzipSink); refused before anything is opened
         if output_parts and int(output_parts) > 1:
@@ -315,6 +329,11 @@ def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
         report.close()
 
 
+def _is_paired(pipe):
+    """The pipeline takes pairs (``run(batch1, batch2)``): the paired pipeline or the legacy one."""
+    return isinstance(pipe, PairedTrimPipeline)
+
+
 def pipe_demultiplexes(pipe, paths_out, merged_out=None):
     return bool(getattr(pipe, "demultiplex", False)) or any(
         p is not None and "{name}" in str(p) for p in list(paths_out) + [merged_out])
@@ -325,7 +344,9 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
     """The chunk loop of ``_trim_stream``; ``report``: the run's TrimReport or None; ``device_gzip``: the main
     outputs and the merged output through ``fastq.DeviceGzipSink`` (side files stay on the host path);
     ``device_gunzip``: BGZF ``.gz`` input inflated on the GPU (``fastq.ChunkedFastqReader``)."""
-    paired = len(paths_in) == 2
+    paired = _is_paired(pipe)
+    interleaved_in = paired and len(paths_in) == 1
+    interleaved_out = paired and len(paths_out) == 1
     first = pipe.p1 if paired else pipe
     merging = paired and pipe.merge_overlapping
     TrimStats.check(pipe.stats, first.discard_trimmed, first.discard_untrimmed, merging)
@@ -340,22 +361,25 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
         demux_paths = pipe._demux_paths(paths_out[0])
         pipe.demux_counts = {}
     else:
-        sinks = [make_sink(p, output_parts, chunk_bytes + (64 << 20) + 32, be, clock, keep=keep_output, device_gzip=device_gzip)
-                 for p in paths_out]
+        # (an interleaved output takes both reads' text of a chunk: twice the room, as the merged output below)
+        room = chunk_bytes + (64 << 20)
+        sinks = [make_sink(p, output_parts, (2 * room if interleaved_out else room) + 32, be, clock, keep=keep_output,
+                           device_gzip=device_gzip) for p in paths_out]
     aux_files = {kind: open_by_extension(path) for kind, path in (pipe.aux or {}).items()}
     dest_codes = {name: code for code, name in DEST_NAMES.items()}
     dest_files = {dest_codes[kind]: [open_by_extension(p) for p in (paths if paired else (paths,))]
                   for kind, paths in pipe.outputs.items()                # (paired: a path per read)
                   if not (demux and kind == "untrimmed")}                # (demultiplexing: that path is the last group's)
+    merged_sink = None
     if merging:
         totals["merged"] = 0
         if merged_out is not None:
             # a merged record is at most its two input records, and each input chunk may carry up to 64 MB over
-            sinks.append(make_sink(merged_out, output_parts, 2 * (chunk_bytes + (64 << 20)) + 32, be, clock, keep=keep_output,
-                                   device_gzip=device_gzip))
+            merged_sink = make_sink(merged_out, output_parts, 2 * (chunk_bytes + (64 << 20)) + 32, be, clock, keep=keep_output,
+                                    device_gzip=device_gzip)
     stats = TrimStats(pipe.stats, paired, first.quality_base) if pipe.stats else None
     try:
-        for batches in read_chunks(paths_in, chunk_bytes, be, clock, byte_ranges, device_gunzip):
+        for batches in read_chunks(paths_in, chunk_bytes, be, clock, byte_ranges, device_gunzip, interleaved=interleaved_in):
             t0 = time.perf_counter()
             if stats is not None and stats.pre is not None:
                 stats.pre.collect_batch(*batches)             # before any stage writes into the chunks
@@ -366,6 +390,8 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
                 grouped, edges = be.fastq_emit_grouped(res.batch.data, res.batch.records, res.begin, res.end, res.ubegin,
                                                        res.uend, res.group, len(res.group_names))
                 per_group = torch.bincount(res.group[res.group >= 0].to(torch.int64), minlength=len(res.group_names)).cpu().tolist()
+            elif interleaved_out:
+                texts = [res.device_text_interleaved(_lib.DEST_KEEP)]
             else:
                 texts = [be.fastq_emit(r.batch.data, r.batch.records, r.begin, r.end, r.ubegin, r.uend, r.dest,
                                        _lib.DEST_KEEP) for r in reads]
@@ -387,8 +413,8 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
                             demux_files[g] = open_by_extension(demux_paths[g])
                         demux_files[g].write(memoryview(host[edges[g]:edges[g + 1]]))
                         pipe.demux_counts[name] = pipe.demux_counts.get(name, 0) + per_group[g]
-            if len(sinks) == 3:
-                sinks[2].write(res.merged if res.merged is not None else texts[0][:0])
+            if merged_sink is not None:
+                merged_sink.write(res.merged if res.merged is not None else texts[0][:0])
             if aux_files:                                     # host-assembled lines (debugging outputs, not a throughput path)
                 for kind, blob in res.aux_text(tuple(aux_files)).items():
                     aux_files[kind].write(blob)
@@ -402,7 +428,8 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
         if report is not None:
             pipe.report_summary = report.summary()
     finally:
-        for obj in sinks + list(aux_files.values()) + [fh for fhs in dest_files.values() for fh in fhs]:
+        for obj in sinks + ([merged_sink] if merged_sink is not None else []) + list(aux_files.values()) + [
+                fh for fhs in dest_files.values() for fh in fhs]:
             obj.close()
         if demux:
             for fh in demux_files.values():
@@ -565,6 +592,8 @@ class TrimPipeline(object):
             m.rounds.append((took, best.clone(), which.clone(), begin.clone(), end.clone()))
         if m.last_which is not None:
             m.last_which = torch.where(took, which, m.last_which)
+            if m.foreign is not None:                                     # (a match of its own replaces the copied one)
+                m.foreign = (m.foreign[0] & ~took, m.foreign[1])
         if m.sides is not None:                                           # Match.front / _guess_is_front of this round's match
             code = codes[which]
             is_front = torch.where(code == 2, best[:, 2] == 0, code == 1)
@@ -764,6 +793,7 @@ class TrimPipeline(object):
         lens = (m.end - m.begin).clamp(min=0).cpu().tolist()
         took = m.matched.cpu().tolist()
         which = m.last_which.cpu().tolist() if m.last_which is not None else None
+        foreign = m.foreign[0].cpu().tolist() if m.foreign is not None else None
         tag = self.length_tag
         regex = re.compile(r"\b" + tag + r"[0-9]*\b") if tag else None
         names, offs, cur = [], [], 0
@@ -776,7 +806,8 @@ class TrimPipeline(object):
                 if name.endswith(sfx):
                     name = name[:-len(sfx)]
             if self.prefix or self.suffix:
-                ad = self.adapters[which[i]].name if (which is not None and took[i]) else "no_adapter"
+                ads = m.foreign[1] if (foreign is not None and foreign[i]) else self.adapters
+                ad = ads[which[i]].name if (which is not None and took[i]) else "no_adapter"
                 name = self.prefix.replace("{name}", ad) + name + self.suffix.replace("{name}", ad)
             blob = name.encode("latin-1")
             names.append(blob)
@@ -879,6 +910,17 @@ class PairedTrimResult(object):
     def text(self, which=_lib.DEST_KEEP):
         return self.read1.text(which), self.read2.text(which)
 
+    def device_text_interleaved(self, which=_lib.DEST_KEEP):
+        """``text_interleaved`` as a uint8 device tensor (one ``atr_fastq_emit_pairs``)."""
+        r1, r2 = self.read1, self.read2
+        return r1.batch.backend.fastq_emit_pairs(r1.batch, r1.begin, r1.end, r1.ubegin, r1.uend,
+                                                 r2.batch, r2.begin, r2.end, r2.ubegin, r2.uend, self.dest, which)
+
+    def text_interleaved(self, which=_lib.DEST_KEEP):
+        """Formatted FASTQ text (bytes) of the pairs sent to destination ``which``, read 1 then read 2 of every pair:
+        what the reference's ``-L`` file holds (InterleavedFormatter, io/seqio.py:740-749)."""
+        return bytes(self.device_text_interleaved(which).cpu().numpy().tobytes())
+
 
 class PairedTrimPipeline(object):
     """Paired-end trimming in "both" mode (both reads are modified; trim/cli.py:633-648) as
@@ -891,7 +933,14 @@ class PairedTrimPipeline(object):
     (commands/trim/modifiers.py:864-931, trim/__init__.py:546-552): pairs whose reads overlap by
     ``merge_min_overlap`` (a fraction of the shorter read up to 1, else bases) at ``merge_error_rate``
     become ONE read -- destination ``DEST_MERGED``, text in ``PairedTrimResult.merged`` -- corrected
-    first with ``correct_mismatches`` unless the insert aligner already saw the pair."""
+    first with ``correct_mismatches`` unless the insert aligner already saw the pair.
+    ``overwrite_low_quality`` = (lowq, highq, window): OverwriteRead (``-w``, modifiers.py:511-563) at ``W``'s place in
+    ``op_order``: a read whose first ``window`` kept qualities average below ``lowq`` while its mate's average at
+    least ``highq`` is replaced by the mate's reverse complement (``_overwrite_stage``); ``self.overwritten`` counts
+    them per read.  ``lowq > highq`` and ``window < 1`` are a ValueError.  Refused with it (NotImplementedError; the
+    reference runs them): ``aux`` files (the clone's match_info lines), ``report=True``, ``stats`` post,
+    ``cut_min`` / ``cut_min2`` and ``bisulfite`` (both read ``clipped[]``, which the clone copies unmirrored),
+    ``merge_overlapping`` (the ``corrected`` flag), linked adapters."""
 
     def __init__(self, adapters1=(), adapters2=(), aligner="adapter", times=1, action="trim", cut=(), cut2=(),
                  nextseq_trim=None, quality_cutoff=None, quality_base=33, trim_n=False, minimum_length=None,
@@ -899,8 +948,26 @@ class PairedTrimPipeline(object):
                  op_order="CGQAW", insert_args=None, correct_mismatches=None, merge_overlapping=False,
                  merge_min_overlap=0.9, merge_error_rate=0.2, aux=None, length_tag=None, strip_suffix=(), prefix="",
                  suffix="", zero_cap=False, outputs=None, cut_min=(), cut_min2=(), bisulfite=None, bisulfite2=None,
-                 stats=None, report=False):
+                 stats=None, report=False, overwrite_low_quality=None):
         self.stats = _stats_modes(stats)                                  # as TrimPipeline's: trim_files' summary
+        # -w LOWQ,HIGHQ,WINDOW (OverwriteRead, modifiers.py:511-563): the stage at W's place in op_order; the reads it
+        # overwrote, per read of the pair, add up in self.overwritten
+        self.overwrite_low_quality, self.overwritten = None, [0, 0]
+        if overwrite_low_quality is not None:
+            lowq, highq, window = (int(v) for v in overwrite_low_quality)
+            if lowq > highq:
+                raise ValueError("For --overwrite-low-quality, LOWQ must be <= HIGHQ")           # cli.py:745-748
+            if window < 1:
+                raise ValueError("--overwrite-low-quality: WINDOW must be at least 1")
+            self.overwrite_low_quality = (lowq, highq, window)
+            for given, what in ((aux, "--info-file / --rest-file / --wildcard-file (the clone's match_info lines)"),
+                                (report, "report=True"), ("post" in self.stats, "--stats post / both"),
+                                (cut_min or cut_min2, "--cut-min / --cut-min2 (the clone copies clipped[] unmirrored)"),
+                                (bisulfite or bisulfite2, "--bisulfite (the clone copies clipped[] unmirrored)"),
+                                (merge_overlapping, "--merge-overlapping (the clone's corrected flag)"),
+                                (any(isinstance(a, LinkedAdapter) for a in list(adapters1) + list(adapters2)), "linked adapters")):
+                if given:
+                    raise NotImplementedError("--overwrite-low-quality with " + what)
         self.report = bool(report)                                        # as TrimPipeline's: trim_files' report_summary
         if self.report:
             check_envelope(aligner=aligner, merge_overlapping=bool(merge_overlapping), bisulfite=bool(bisulfite or bisulfite2))
@@ -1013,6 +1080,63 @@ class PairedTrimPipeline(object):
         # insert match
         return insert_matched, (self._count_corrected(corrected) if correct >= 0 else None)
 
+    def _overwrite_stage(self, mate1, mate2):
+        """OverwriteRead over the batch (commands/trim/modifiers.py:538-563) on the reads as they are now: where one
+        read's first WINDOW kept qualities average below LOWQ and the other's at least HIGHQ, the worse read becomes
+        the reverse complement of the better one -- real text appended to the worse read's chunk
+        (atr_overwrite_plan_batch + atr_overwrite_apply_batch), its record re-pointed, its interval the whole clone,
+        its adapter flag (and last adapter) the better read's."""
+        from .modifiers import COMP_TABLE
+        lowq, highq, window = self.overwrite_low_quality
+        mates = (mate1, mate2)
+        n = len(mate1.batch)
+        if n == 0:
+            return
+        for m in mates:                                                   # the reference's clone carries the N's
+            if m.ubegin is not None:
+                write_mask(m.batch, m.begin, m.end, m.ubegin, m.uend)
+                m.ubegin = m.uend = None
+        b1, b2 = mate1.batch, mate2.batch
+        be = b1.backend
+        which, grow1, grow2 = be.overwrite_plan(b1, mate1.begin, mate1.end, b2, mate2.begin, mate2.end, lowq, highq, window,
+                                                self.p1.quality_base)
+        need = (int(grow1[n].item()), int(grow2[n].item()))
+        if not any(need):
+            return
+        shared = b1.data.data_ptr() == b2.data.data_ptr()                 # (an interleaved chunk: one tail behind the other)
+
+        def grown(data, extra):
+            base = (data.numel() + 15) // 16 * 16
+            if base + extra >= (1 << 32) - 16:
+                raise ValueError("the chunk and its rewritten names must stay below 4 GiB")
+            pad = torch.zeros((base - data.numel() + extra + 16,), dtype=torch.uint8, device=data.device)
+            return torch.cat([data, pad]), base
+
+        if shared:
+            data1, tail1 = grown(b1.data, need[0] + need[1])
+            data2, tail2 = data1, tail1 + need[0]
+            ends = (tail1 + need[0] + need[1],) * 2
+        else:
+            (data1, tail1), (data2, tail2) = grown(b1.data, need[0]), grown(b2.data, need[1])
+            ends = (tail1 + need[0], tail2 + need[1])
+        rec1, rec2 = b1.records.clone(), b2.records.clone()
+        err = be.overwrite_apply(data1, rec1, mate1.begin, mate1.end, data2, rec2, mate2.begin, mate2.end, which, grow1, grow2,
+                                 tail1, tail2, COMP_TABLE)
+        if err != _lib.INT64_MAX:
+            raise KeyError("--overwrite-low-quality: pair %d: base without a complement" % (err // 8))
+        # (nbytes covers the clones: the read-name modifiers read the names from the chunk's first nbytes)
+        mate1.batch = FastqBatch(data1, max(b1.nbytes, ends[0]), rec1, be, b1.line_ends, b1.stride)
+        mate2.batch = FastqBatch(data2, max(b2.nbytes, ends[1]), rec2, be, b2.line_ends, b2.stride)
+        first, second = which == 1, which == 2
+        m1, m2 = mate1.matched, mate2.matched
+        mate1.matched, mate2.matched = torch.where(first, m2, m1), torch.where(second, m1, m2)
+        if mate1.last_which is not None:
+            w1, w2 = mate1.last_which, mate2.last_which
+            mate1.last_which, mate2.last_which = torch.where(first, w2, w1), torch.where(second, w1, w2)
+            mate1.foreign, mate2.foreign = (first, self.p2.adapters), (second, self.p1.adapters)
+        self.overwritten[0] += int(first.sum().item())
+        self.overwritten[1] += int(second.sum().item())
+
     def _count_corrected(self, corrected):
         """ErrorCorrectorMixin's counters over the changed-base counts of a batch; returns the pairs with a change."""
         pairs = (corrected.sum(dim=1) > 0).to(torch.uint8)
@@ -1107,7 +1231,8 @@ class PairedTrimPipeline(object):
             raise ValueError("the two FASTQ batches hold different numbers of records")
         pipes, mates = (self.p1, self.p2), (_Mate(self.p1, batch1), _Mate(self.p2, batch2))
         insert = (lambda: self._insert_stage(*mates)) if self.aligner == "insert" else None
-        insert_matched, already_corrected = _run_stages(pipes, mates, insert) or (None, None)
+        overwrite = (lambda: self._overwrite_stage(*mates)) if self.overwrite_low_quality else None
+        insert_matched, already_corrected = _run_stages(pipes, mates, insert, overwrite) or (None, None)
         masks = [pipe._filter_stage(m, masks=True) for pipe, m in zip(pipes, mates)]
         dest = batch1.backend.pair_filter_batch(masks[0], masks[1], self.min_affected)
         merged_text = None
@@ -1125,10 +1250,20 @@ class PairedTrimPipeline(object):
             dest = torch.where(merged, torch.full_like(dest, DEST_MERGED), dest)
         return PairedTrimResult(self.p1._result(mates[0], dest), self.p2._result(mates[1], dest), merged_text)
 
-    def trim_files(self, in1, in2, out1, out2, chunk_bytes=128 << 20, merged_out=None, keep_output=False, output_parts=1,
+    def trim_files(self, in1, in2, out1, out2=None, chunk_bytes=128 << 20, merged_out=None, keep_output=False, output_parts=1,
                    device_gzip=False, device_gunzip=False):
         """Stream two FASTQ files through the GPU in lock step (chunks of whole records, the
-        same number from each file); returns the destination counts.  ``merged_out``: the
+        same number from each file); returns the destination counts.
+
+        ``in2=None``: ``in1`` is an INTERLEAVED file, read 1 and read 2 of every pair in turn (the reference's
+        ``-l``; ``fastq.read_chunks(interleaved=True)``): an odd number of records is a ``FormatError``, the names of
+        the two reads are not compared.  ``out2=None``: ``out1`` is written interleaved (the reference's ``-L``):
+        one formatter call (``atr_fastq_emit_pairs``) and one sink per chunk; ``device_gzip`` and ``output_parts``
+        act on that sink as on any other.  A merged output stays a file of its own.  Interleaved output together
+        with the filtered pairs' own files (``outputs=``) is a NotImplementedError: the reference interleaves those
+        files too (trim/__init__.py:568-573), which is not provided.
+
+        ``merged_out``: the
         --merged-output file (without it merged reads are dropped, as by the reference).
         ``output_parts`` > 1: every output as that many part files (``TrimPipeline.trim_file``); part i of
         ``out1`` and part i of ``out2`` hold the same pairs in the same order.  ``device_gzip``: the outputs
@@ -1138,8 +1273,8 @@ class PairedTrimPipeline(object):
             raise NotImplementedError("device_gzip with demultiplexed outputs ({name} in the output path)")
         if any(p is not None and "{name}" in str(p) for p in (out1, out2, merged_out)):
             raise ValueError("Demultiplexing not supported for paired-end files, yet.")        # trim/cli.py:769-771
-        return _trim_stream(self, [in1, in2], [out1, out2], chunk_bytes, keep_output, output_parts, merged_out,
-                            device_gzip=device_gzip, device_gunzip=device_gunzip)
+        return _trim_stream(self, [in1] if in2 is None else [in1, in2], [out1] if out2 is None else [out1, out2], chunk_bytes,
+                            keep_output, output_parts, merged_out, device_gzip=device_gzip, device_gunzip=device_gunzip)
 
     def trim_bytes(self, data1, data2, which=_lib.DEST_KEEP):
         """Two FASTQ texts in (same number of records), the two trimmed texts out."""
@@ -1237,9 +1372,22 @@ def pipeline_from_args(argv, paired_input=False, report=False):
     ap.add_argument("--info-file", default=None)
     ap.add_argument("--rest-file", "-r", default=None)
     ap.add_argument("--wildcard-file", default=None)
+    ap.add_argument("-w", "--overwrite-low-quality", default=None)
+    ap.add_argument("-l", "--interleaved-input", default=None)
+    ap.add_argument("-L", "--interleaved-output", default=None)
     o = ap.parse_args(argv)
+    paired_input = bool(paired_input or o.interleaved_input)              # (-l is paired input, cli.py:614-618)
+    overwrite = None
+    if o.overwrite_low_quality:                                           # three comma-separated ints (cli.py:284-291)
+        overwrite = tuple(int(v) for v in str(o.overwrite_low_quality).split(","))
+        if len(overwrite) != 3:
+            raise ValueError("--overwrite-low-quality takes LOWQ,HIGHQ,WINDOW")
     paired = bool(o.adapters2 or o.front2 or o.anywhere2 or o.cut2 or o.cut_min2 or o.pair_filter or o.aligner == "insert" or
-                  o.merge_overlapping)
+                  o.merge_overlapping or (overwrite and paired_input))
+    if overwrite and not paired_input:
+        raise ValueError("--overwrite-low-quality is not valid for single-end reads")     # cli.py:741-744
+    if overwrite and overwrite[0] > overwrite[1]:
+        raise ValueError("For --overwrite-low-quality, LOWQ must be <= HIGHQ")              # cli.py:745-748
     for cm in (o.cut_min, o.cut_min2):                                     # cli.py:810-830
         if len(cm) > 2:
             raise ValueError("You cannot remove bases from more than two ends.")
@@ -1247,12 +1395,10 @@ def pipeline_from_args(argv, paired_input=False, report=False):
             raise ValueError("You cannot remove bases from the same end twice.")
     if paired_input:
         # cli.py:630-641, the reference's own list: any of these asks for full paired-end trimming, none of them is its
-        # legacy mode.  The list there also names interleaved_input and overwrite_low_quality: this parser has neither
-        # option (argparse refuses them), so they cannot be set here -- whoever adds them must add them to `full` too, or
-        # such a run would silently take the legacy pipeline.  (--aligner insert and -R are NOT on it: the reference then modifies read 1 alone, which the insert
+        # legacy mode.  (--aligner insert and -R are NOT on it: the reference then modifies read 1 alone, which the insert
         # aligner and the merge stage have no meaning for -- refused here rather than run as something else)
         full = bool(o.adapters2 or o.front2 or o.anywhere2 or o.cut2 or o.cut_min2 or o.quality_cutoff or o.trim_n or
-                    o.pair_filter or o.too_short_paired_output or o.too_long_paired_output)
+                    o.pair_filter or o.too_short_paired_output or o.too_long_paired_output or o.interleaved_input or overwrite)
         if not full and (o.aligner == "insert" or o.merge_overlapping):
             raise NotImplementedError("--aligner insert / --merge-overlapping with paired-end input and none of the options "
                                       "that switch the reference's legacy mode off (trim/cli.py:630-641)")
@@ -1310,7 +1456,7 @@ def pipeline_from_args(argv, paired_input=False, report=False):
     adapters2 = parser.parse_multi(o.adapters2, o.anywhere2, o.front2) if paired else []
     if (not adapters and not adapters2 and not qc and o.nextseq_trim is None and not o.cut and not o.cut2 and
             (o.minimum_length is None or o.minimum_length <= 0) and o.maximum_length is None and not o.trim_n and
-            o.max_n is None):
+            o.max_n is None and not overwrite):
         raise ValueError("You need to provide at least one adapter sequence.")        # trim/__init__.py:386-404
     if action == "mask" and any(isinstance(a, LinkedAdapter) for a in adapters + adapters2):
         raise NotImplementedError("--mask-adapter with a linked adapter: the reference's AdapterCutter fails on it "
@@ -1371,6 +1517,21 @@ def pipeline_from_args(argv, paired_input=False, report=False):
         outputs = {kind: (path, second[kind]) for kind, path in outputs.items()}
     if legacy and (aux or outputs or o.length_tag or o.strip_suffix or o.prefix or o.suffix or o.zero_cap):
         raise NotImplementedError("side files and read-name modifiers with paired-end input in legacy mode")
+    if o.interleaved_output and outputs:
+        raise NotImplementedError("interleaved output with --too-short-output / --too-long-output / --untrimmed-output "
+                                  "(the reference interleaves those files as well)")
+    if o.interleaved_output and not (paired or legacy):                   # (-l alone made the input paired above)
+        raise ValueError("interleaved output needs paired-end input")
+    pipe = _pipeline_from_options(o, paired, legacy, adapters, adapters2, common, bis1, bis2, aux, outputs, insert_args,
+                                  overwrite)
+    # the two paths are the caller's to hand to trim_files (in2=None / out2=None)
+    pipe.interleaved_input, pipe.interleaved_output = o.interleaved_input, o.interleaved_output
+    return pipe
+
+
+def _pipeline_from_options(o, paired, legacy, adapters, adapters2, common, bis1, bis2, aux, outputs, insert_args,
+                           overwrite=None):
+    """The pipeline object of ``pipeline_from_args`` once its options are checked."""
     if not paired:
         first = TrimPipeline(adapters=adapters, cut=o.cut, cut_min=o.cut_min, bisulfite=bis1, aux=aux or None, outputs=outputs or None, length_tag=o.length_tag,
                              strip_suffix=o.strip_suffix, prefix=o.prefix, suffix=o.suffix, zero_cap=o.zero_cap, **common)
@@ -1378,7 +1539,7 @@ def pipeline_from_args(argv, paired_input=False, report=False):
     return PairedTrimPipeline(outputs=outputs or None, aux=aux or None, length_tag=o.length_tag, strip_suffix=o.strip_suffix, prefix=o.prefix,
                               suffix=o.suffix, zero_cap=o.zero_cap, adapters1=adapters, adapters2=adapters2, aligner=o.aligner, cut=o.cut, cut2=o.cut2,
                               cut_min=o.cut_min, cut_min2=o.cut_min2, bisulfite=bis1, bisulfite2=bis2,
-                              pair_filter=o.pair_filter or "any", insert_args=insert_args,
+                              pair_filter=o.pair_filter or "any", insert_args=insert_args, overwrite_low_quality=overwrite,
                               correct_mismatches=o.correct_mismatches, merge_overlapping=o.merge_overlapping,
                               merge_min_overlap=o.merge_min_overlap,
                               merge_error_rate=0.2 if o.merge_error_rate is None else o.merge_error_rate, **common)

@@ -662,6 +662,54 @@ int atr_fastq_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, co
                    const uint8_t *d_dest, int dest, int64_t n, int record_bytes_hint, int64_t *d_offsets, void *d_work,
                    uint8_t *d_out, void *stream);
 
+/* Interleaved output (InterleavedFormatter, io/seqio.py:740-749): FastqFormat.format_entry of read 1 and then of
+ * read 2 of every pair with d_dest[p] == dest (d_dest NULL: every pair), in pair order, into ONE text.  The two
+ * reads have a chunk, a record array, kept intervals and (both or neither) unmasked intervals each; d_bytes1 and
+ * d_bytes2 may be the same chunk (an interleaved input) or different ones, and neither needs to start on a 16-byte
+ * boundary.
+ * PRECONDITION, stricter than atr_fastq_emit's: the kernel loads whole ADDRESS-aligned 16-byte blocks, so up to 15
+ * bytes in front of the first '@' a call formats and behind its last quality byte are READ (never written, never
+ * used).  They must be readable memory: true for any chunk that lies in one allocation aligned to 16 bytes or more
+ * and padded to a multiple of 16 behind its text (what atr_fastq_index asks for already), and for any view into
+ * such a chunk; not true for text that ends exactly at the end of a mapping that is not a multiple of 16 long.
+ * Two calls, as atr_fastq_emit: with d_out == NULL d_offsets[n + 1] (device int64) receives the exclusive
+ * prefix sums of the pairs' formatted sizes (d_offsets[n] = total bytes); with d_out of that many bytes the text is
+ * written.  d_work: scratch of atr_fastq_emit_pairs_work_bytes(n) bytes.  pair_bytes_hint: average input bytes per
+ * pair (0: unknown) -- only picks how many pairs a wave stages at once.  The offsets are made without global
+ * atomics: equal inputs give equal bytes. */
+size_t atr_fastq_emit_pairs_work_bytes(int64_t n);
+int atr_fastq_emit_pairs(const uint8_t *d_bytes1, const atr_fastq_record *d_records1, const int32_t *d_begin1,
+                         const int32_t *d_end1, const int32_t *d_unmasked_begin1, const int32_t *d_unmasked_end1,
+                         const uint8_t *d_bytes2, const atr_fastq_record *d_records2, const int32_t *d_begin2,
+                         const int32_t *d_end2, const int32_t *d_unmasked_begin2, const int32_t *d_unmasked_end2,
+                         const uint8_t *d_dest, int dest, int64_t n, int pair_bytes_hint, int64_t *d_offsets, void *d_work,
+                         uint8_t *d_out, void *stream);
+
+/* OverwriteRead (`-w LOWQ,HIGHQ,WINDOW`, commands/trim/modifiers.py:511-563; the W of --op-order), on the kept
+ * intervals of the two reads of every pair, in two steps like atr_merge_plan_batch / atr_merge_emit_batch.
+ * Plan: d_which[p] = 0 (nothing; also when a read is shorter than the window), 1 (read 1 is overwritten: the sum of
+ * read 1's first `window` kept qualities minus the base is < lowq * window and read 2's is >= highq * window) or 2 (the
+ * other way round); d_grow1 / d_grow2 [n + 1] (device int64): exclusive prefix sums of the bytes the chunk of read
+ * 1 / read 2 must grow by -- name + bases + qualities of every clone, 16-byte padded -- [n] = the total.  d_work:
+ * atr_overwrite_work_bytes(n) bytes.  lowq > highq, window < 1: ATR_ERR_INVALID.
+ * Apply: the caller has grown the chunks (zeroed) so that the clones of read 1 fit from byte tail1 of d_bytes1 on and
+ * those of read 2 from tail2 of d_bytes2 (one chunk for both reads: one tail behind the other); the chunks with
+ * their tails must stay below 4 GiB.  Every clone -- the better read's name, its kept bases through comp[] (0: no
+ * complement) in reverse order, its kept qualities reversed -- is written there, and the overwritten read's
+ * descriptor (flag bit 0 from the better read), begin (0) and end (the clone's length) are re-pointed IN PLACE.
+ * *d_error: min over failing pairs of pair * 8 + 1 (a base without a complement, the reference's KeyError), or
+ * INT64_MAX. */
+size_t atr_overwrite_work_bytes(int64_t n);
+int atr_overwrite_plan_batch(const uint8_t *d_bytes1, const atr_fastq_record *d_records1, const int32_t *d_begin1,
+                             const int32_t *d_end1, const uint8_t *d_bytes2, const atr_fastq_record *d_records2,
+                             const int32_t *d_begin2, const int32_t *d_end2, int64_t n, int lowq, int highq, int window,
+                             int quality_base, uint8_t *d_which, int64_t *d_grow1, int64_t *d_grow2, void *d_work,
+                             void *stream);
+int atr_overwrite_apply_batch(uint8_t *d_bytes1, atr_fastq_record *d_records1, int32_t *d_begin1, int32_t *d_end1,
+                              uint8_t *d_bytes2, atr_fastq_record *d_records2, int32_t *d_begin2, int32_t *d_end2, int64_t n,
+                              const uint8_t *d_which, const int64_t *d_grow1, const int64_t *d_grow2, int64_t tail1,
+                              int64_t tail2, const uint8_t comp[256], int64_t *d_error, void *stream);
+
 /* Demultiplexing (`{name}` in the output path; commands/trim/writers.py:119-154): atr_fastq_emit for many
  * outputs in one pass.  d_group[r] (device int32) is the output of record r, 0 .. n_groups-1; any other value: the
  * record is not written.  The records of output 0 come first in d_out, then those of output 1 ...; inside an
