@@ -91,7 +91,7 @@ inline FastWork fast_carve(void *work, long long nreads, int nbins = FILTER_BINS
     return w;
 }
 // what the first half of a plane64 locate call (piece_kernels.hip: launch_planes_prepass) hands to its second half
-struct PlanesCall { FastWork wk; int nw; };
+struct PlanesCall { FastWork wk; int nw; void *tail = nullptr; };   // tail: atr_tail_spec of the run-time compiled pre-pass that served the call
 
 // ATR_FUSED_SCAN=0: the two scan launches instead of the atomics (A/B switch)
 inline bool fast_fused_scan() {

@@ -7,7 +7,8 @@
 //                                 their planes) and take the full bit-vector sweep at the end of the kernel, 64 to a wave
 //   K2  scan_bins / scan_total    (locate_fast.hpp, unchanged)
 //   P3  piece_scatter_kernel      the block's list -> the bins of `order`
-//   K4a / K4                      band_kernel / window_kernel<.., PLANES>: the exact DP, reading plane64
+//   K4a / K4                      band_kernel / window_kernel<.., PLANES>: the exact DP, reading plane64 -- or, behind the
+//                                 run-time compiled pre-pass, ONE launch of the run-time compiled tail (tail_filter.hpp)
 //
 // Same records as the one-pass pipeline (filter_kernels.hip) and as the full sweep; tests/test_gpu_locate.py
 // compares all three on every size.
@@ -122,6 +123,14 @@ static const jit::SpecKernel *piece_spec_for(const atr_aligner *a, const FilterP
     return jit::spec_kernel(a, fp, pp, nw, ragged, ragged ? 32 * nw : max_len, compile, ascii_stride);
 }
 
+// The run-time compiled DP tail (tail_filter.hpp: atr_tail_spec, a second kernel of the pre-pass object) serves wherever the
+// specialised pre-pass does.  ATR_TAIL_SPEC=0, read at every call, brings the band_kernel || window_kernel pair back (A/B
+// on one build); so do ATR_JIT=0 and a failed compile, which leave no such object.
+static bool tail_spec_enabled() {
+    const char *x = getenv("ATR_TAIL_SPEC");
+    return !(x && x[0] == '0');
+}
+
 // 1: a specialised kernel is ready for (aligner, max_len, ragged) on the current device; 0: there is none (outside the
 // two-pass envelope, ATR_JIT=0, no hiprtc, compile error) -- the generic kernel then serves the calls.
 int prepare_locate_planes(const atr_aligner *a, int max_len, bool ragged) {
@@ -169,6 +178,7 @@ int launch_planes_prepass(const atr_aligner *a, const uint4 *planes, const int32
     }
     pc->wk = wk;
     pc->nw = nw;
+    pc->tail = sk ? (void *)sk->tail : nullptr;
     return (int)hipGetLastError();
 }
 
@@ -177,6 +187,16 @@ int launch_planes_tail(const atr_aligner *a, const uint4 *planes, const int32_t 
     FastWork wk = pc.wk;
     if (!wk.fused) launch_fast_scan(wk, st);
     hipLaunchKernelGGL(piece_scatter_kernel, dim3(wk.nused), dim3(256), 0, st, nreads, a->p.m, wk);
+    if (pc.tail && !one_stream && tail_spec_enabled()) {
+        // one launch on the caller's stream: window blocks first, the band blocks behind them (no side stream, fork or join)
+        {
+            const bool small = nreads <= 65536;                     // (the grids of launch_fast_dp)
+            const int win_blocks = (int)std::max<long long>(1, std::min<long long>((nreads + 3) / 4, 1024));
+            const int band_blocks = (int)std::max<long long>(1, std::min<long long>(small ? (nreads + 3) / 4 : (nreads + 255) / 256, 4096));
+            const hipError_t rc = jit::tail_launch((hipFunction_t)pc.tail, win_blocks, band_blocks, planes, lens, pc.nw, max_len, out, wk, st);
+            return rc != hipSuccess ? (int)rc : (int)hipGetLastError();
+        }
+    }
     return launch_fast_dp(a, planes, lens, nreads, pc.nw, max_len, out, wk, nullptr, 0, 1, st, /*planes=*/true, one_stream);
 }
 
@@ -217,6 +237,7 @@ int launch_locate_ascii_fused(const atr_aligner *a, const uint8_t *ascii, long l
     PlanesCall pc;
     pc.wk = wk;
     pc.nw = nw;
+    pc.tail = (void *)sk->tail;
     return launch_planes_tail(a, planes, lens, nreads, max_len, out, pc, st, false);
 }
 

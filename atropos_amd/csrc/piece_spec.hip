@@ -24,3 +24,8 @@ void atr_piece_spec(const uint4 *__restrict__ planes, const int32_t *__restrict_
                                                              max_len, out, wk);
 }
 #endif
+
+// the aligner's DP tail in the same code object (jit.hpp hands tail_spec.hip and its tail_spec_config.h over as well)
+#ifdef ATR_TAIL_SPEC
+#include "tail_spec.hip"
+#endif

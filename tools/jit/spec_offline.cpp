@@ -1,7 +1,9 @@
 // tools/jit/spec_offline.cpp -- writes the piece_spec_config.h jit.hpp would generate for an aligner, so that
 // piece_spec.hip can be compiled with hipcc offline (ISA inspection, resource counts; tools/jit/spec_offline.sh).
 //   spec_offline <adapter> <max_error_rate> <flags> <min_overlap> <max_len> <ragged 0|1> <out_dir> [--rtc]
-// --rtc: also run the very hiprtc path of the library (no GPU needed) and write the code object to <out_dir>/spec.hsaco.
+// Also writes the tail_spec_config.h of the aligner's run-time compiled DP tail (tail_spec.hip, tail_filter.hpp).
+// --rtc: also run the very hiprtc path of the library (no GPU needed) and write the code objects to <out_dir>/spec.hsaco
+// and <out_dir>/tail.hsaco.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,15 +33,26 @@ int main(int argc, char **argv) {
     if (!f) { perror("open"); return 1; }
     fwrite(cfg.data(), 1, cfg.size(), f);
     fclose(f);
+    const std::string tcfg = jit::tail_config(a);
+    f = fopen((dir + "/tail_spec_config.h").c_str(), "w");
+    if (!f) { perror("open"); return 1; }
+    fwrite(tcfg.data(), 1, tcfg.size(), f);
+    fclose(f);
     printf("NW=%d RAGGED=%d n=%d blen=%d llen=%d tlen=%d steps=%d xlo=%d xhi=%d ovl_a=0x%x\n", nw, (int)ragged, n, pp.blen, pp.llen, pp.tlen, pp.steps, pp.xlo, pp.xhi, pp.ovl_a);
     if (argc > 8 && !strcmp(argv[8], "--rtc")) {
         std::string log;
-        const std::vector<char> code = jit::compile_spec(cfg, nw, ragged, 0, "gfx950", &log);
+        const std::vector<char> code = jit::compile_spec(cfg, nw, ragged, 0, "gfx950", &log, &tcfg);
         if (code.empty()) { fprintf(stderr, "hiprtc failed:\n%s\n", log.c_str()); return 1; }
         f = fopen((dir + "/spec.hsaco").c_str(), "wb");
         fwrite(code.data(), 1, code.size(), f);
         fclose(f);
         printf("hiprtc: %zu bytes of code object\n", code.size());
+        const std::vector<char> tcode = jit::compile_tail(tcfg, "gfx950", &log);
+        if (tcode.empty()) { fprintf(stderr, "hiprtc failed on the tail:\n%s\n", log.c_str()); return 1; }
+        f = fopen((dir + "/tail.hsaco").c_str(), "wb");
+        fwrite(tcode.data(), 1, tcode.size(), f);
+        fclose(f);
+        printf("hiprtc: %zu bytes of code object (tail)\n", tcode.size());
     }
     return 0;
 }
