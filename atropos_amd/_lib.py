@@ -188,6 +188,13 @@ PROTOTYPES = {
     "atr_fastq_emit_work_bytes": (C.c_size_t, [C.c_int64]),
     "atr_fastq_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
+    "atr_fasta_work_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "atr_fasta_scan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, STREAM]),
+    "atr_fasta_index": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                  C.c_void_p, C.c_void_p, STREAM]),
+    "atr_fasta_emit_work_bytes": (C.c_size_t, [C.c_int64]),
+    "atr_fasta_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
     "atr_fastq_emit_pairs_work_bytes": (C.c_size_t, [C.c_int64]),
     "atr_fastq_emit_pairs": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 3 + [STREAM]),
     "atr_overwrite_work_bytes": (C.c_size_t, [C.c_int64]),
@@ -242,6 +249,7 @@ REPORT_MAX_WORDS = 1 << 22                # report_core.hpp: the bound of a coun
 REPORT_VARIANTS = {"auto": 0, "lds": 1, "global": 2}
 
 FASTQ_ERR_AT, FASTQ_ERR_PLUS, FASTQ_ERR_NAME2, FASTQ_ERR_LENGTH = 1, 2, 3, 4
+FASTA_ERR_HEADER = 1
 DEST_KEEP, DEST_TOO_SHORT, DEST_TOO_LONG, DEST_TOO_MANY_N, DEST_TRIMMED, DEST_UNTRIMMED = range(6)
 INT64_MAX = (1 << 63) - 1
 EMIT_MAX_GROUPS = 1024                   # atr_fastq_emit_grouped: outputs per call
@@ -930,7 +938,57 @@ class PairTextCalls(object):
         return int(err.item())
 
 
-class HipBackend(AbiCalls, PairTextCalls, StatsCalls):
+class FastaCalls(object):
+    """The wrappers of the FASTA entry points (index and formatter), written against ``_call`` / ``_host`` / ``empty``
+    like ``AbiCalls``' methods.  A mixin of its own: the CPU test-suite serves these entry points from a twin library
+    of their own (tests/emu/emu_fasta.cpp)."""
+
+    def fasta_index(self, data, nbytes):
+        """data: uint8 device tensor holding nbytes of FASTA text (16-byte aligned, zero-padded to the next multiple of
+        16 and 16 bytes more).  Returns (data, records int32 [nrec, 8], record_ends int32 [nrec], tail_end, nlines,
+        error word): ``data`` is the tensor given, or -- when records are wrapped -- a longer one whose tail
+        [padded text, tail_end) holds their sequences in one piece; the records point into it."""
+        info = self.empty((4,), torch.int64)
+        work = self.empty((max(self._host("atr_fastq_work_bytes", nbytes), 16),), torch.uint8)
+        self._call("atr_fastq_count_lines", _ptr(data), nbytes, _ptr(work), _ptr(info))     # (the same lines as FASTQ's)
+        nlines = int(info[0].item())
+        line_ends = self.empty((max(nlines, 1),), torch.int32)
+        work = self.empty((max(self._host("atr_fasta_work_bytes", nbytes, nlines), 16),), torch.uint8)
+        self._call("atr_fasta_scan", _ptr(data), nbytes, _ptr(line_ends), nlines, _ptr(work), C.c_void_p(info.data_ptr() + 8))
+        _, nrec, gather, err = (int(v) for v in info.cpu().tolist())
+        tail_off = (nbytes + 15) // 16 * 16 + 16
+        if gather:
+            if tail_off + gather >= (1 << 32) - 32:
+                raise ValueError("a FASTA chunk and its unwrapped sequences must stay below 4 GiB; read the file in smaller chunks")
+            grown = self.empty((tail_off + (gather + 15) // 16 * 16 + 16,), torch.uint8)
+            have = min(tail_off, data.numel())
+            grown[:have].copy_(data[:have])
+            grown[have:tail_off].zero_()
+            grown[tail_off + gather:].zero_()
+            data = grown
+        records = self.empty((nrec, 8), torch.int32)
+        record_ends = self.empty((nrec,), torch.int32)
+        self._call("atr_fasta_index", _ptr(data), nbytes, _ptr(line_ends), nlines, _ptr(work), nrec, tail_off, gather,
+                   _ptr(records), _ptr(record_ends))
+        return data, records, record_ends, (tail_off + gather if gather else nbytes), nlines, err
+
+    def fasta_emit(self, data, records, begin, end, ubegin, uend, dest, which):
+        """Formatted FASTA text (uint8 device tensor) of the records with dest == which (FASTA or FASTQ records)."""
+        n = records.shape[0]
+        offsets = self.empty((n + 1,), torch.int64)
+        work = self.empty((max(self._host("atr_fasta_emit_work_bytes", n), 16),), torch.uint8)
+        hint = int(data.numel() // max(n, 1))
+        args = (_ptr(data), _ptr(records), _ptr(begin), _ptr(end), _ptr(ubegin), _ptr(uend), _ptr(dest), which, n, hint,
+                _ptr(offsets), _ptr(work))
+        self._call("atr_fasta_emit", *args, None)
+        total = int(offsets[n].item())
+        out = self.empty((max(total, 1),), torch.uint8)
+        if total:
+            self._call("atr_fasta_emit", *args, _ptr(out))
+        return out[:total]
+
+
+class HipBackend(AbiCalls, PairTextCalls, StatsCalls, FastaCalls):
     """Thin object view of the C ABI; all buffers are torch tensors on one GPU.  The calls the CPU test-suite's stand-in
     serves as well are ``AbiCalls``'; here are the plumbing under them and the device-only calls."""
 

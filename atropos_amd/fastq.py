@@ -210,6 +210,138 @@ class FastqBatch(object):
         return out
 
 
+FASTA_SPACE = b" \t\n\r\x0b\x0c\x1c\x1d\x1e\x1f"        # what the FASTA index strips (fasta_core.hpp): str.strip() below 0x80
+_COMPRESSED = (".gz", ".bz2", ".xz")
+
+
+def guess_format(path):
+    """"fasta", "fastq" or None (unknown) from a file name, its compression suffix aside: the reference's
+    ``guess_format_from_name`` over ``splitext_compressed`` (io/seqio.py:958-989).  The formats it knows and this
+    project does not read (colorspace FASTA, SAM / BAM) are a NotImplementedError."""
+    name = os.path.basename(str(path))
+    for sfx in _COMPRESSED:
+        if name.lower().endswith(sfx):
+            name = name[:-len(sfx)]
+            break
+    stem, ext = os.path.splitext(name)
+    ext = ext.lower()
+    if ext in (".fasta", ".fa", ".fna"):
+        return "fasta"
+    if ext in (".fastq", ".fq") or (ext == ".txt" and stem.endswith("_sequence")):
+        return "fastq"
+    if ext in (".csfasta", ".csfa", ".sam", ".bam"):
+        raise NotImplementedError("%s input / output (%r) is not provided" % (ext[1:], str(path)))
+    return None
+
+
+def sniff_format(head):
+    """"fasta" if the first line of ``head`` (bytes) that is neither blank nor a '#' line begins with '>', else
+    "fastq" -- what every input was before FASTA was read (a FASTQ file that begins with '>' is a FormatError either
+    way)."""
+    for line in _universal_newlines(bytes(head)).split(b"\n"):
+        line = line.strip(FASTA_SPACE)
+        if line and not line.startswith(b"#"):
+            return "fasta" if line.startswith(b">") else "fastq"
+    return "fastq"
+
+
+def input_format(path, explicit=None):
+    """The format a file is read as: ``explicit`` ("fasta" | "fastq"), else what its name says (``guess_format``),
+    else what its first byte says once it is decompressed and blank and '#' lines are passed (``sniff_format``; the
+    reference raises UnknownFileType for every name it does not know)."""
+    if explicit is not None:
+        if explicit not in ("fasta", "fastq"):
+            raise ValueError("input_format must be 'fasta' or 'fastq'")
+        return explicit
+    fmt = guess_format(path)
+    if fmt is not None:
+        return fmt
+    name = str(path)
+    if name.endswith(".gz"):
+        import gzip as mod
+    elif name.endswith(".bz2"):
+        import bz2 as mod
+    elif name.endswith(".xz"):
+        import lzma as mod
+    else:
+        mod = None
+    with (mod.open(name, "rb") if mod else open(name, "rb")) as fh:
+        return sniff_format(fh.read(1 << 16))
+
+
+class FastaBatch(FastqBatch):
+    """Whole FASTA records in device memory, the reference's FastaReader (io/seqio.py:233-280) over a chunk: the same
+    descriptors as a FastqBatch with ``qual_off = qual_len = flags = 0``, so every stage that reads names and bases
+    takes it as it is.  A record whose sequence is wrapped over several lines has it in one piece in a tail behind
+    the text (``atr_fasta_index``); ``data`` is then longer than the chunk and ``nbytes`` covers the tail.
+
+    ``record_ends``: per record of the CHUNK the last byte of the line end of its last line (kept for ``head``).
+    One difference from the reference: whitespace is ASCII (``FASTA_SPACE``); it decodes the file as UTF-8, where
+    U+0085 and U+00A0 are stripped too."""
+
+    fmt = "fasta"
+
+    def __init__(self, data, nbytes, records, backend, record_ends=None):
+        FastqBatch.__init__(self, data, nbytes, records, backend, None)
+        self.record_ends = record_ends
+
+    def head(self, nrec):
+        nrec = min(int(nrec), len(self))
+        consumed = int(self.record_ends[nrec - 1].item()) + 1 if nrec else 0
+        return FastaBatch(self.data, self.nbytes, self.records[:nrec], self.backend, self.record_ends), consumed
+
+    def mates(self):
+        raise NotImplementedError("interleaved FASTA is not provided")
+
+    @classmethod
+    def from_bytes(cls, buf, final=True, backend=None):
+        """Index ``buf`` (bytes-like FASTA text that starts at a header, or at the top of the file).
+        final=True: ``buf`` is the rest of the file, a missing last line end is tolerated.  final=False: the records
+        in front of the chunk's LAST header are taken -- that record may go on in the next chunk -- and the number
+        of bytes consumed, the first byte of that header's line, is returned with them.  Returns (batch, consumed)."""
+        be = backend or _lib.get_backend()
+        buf = bytes(buf)
+        if final and len(buf) and not buf.endswith((b"\n", b"\r")):
+            buf += b"\n"
+        nbytes = len(buf)
+        if nbytes >= (1 << 32) - 32:
+            raise ValueError("a FASTA batch must be smaller than 4 GiB; read the file in chunks")
+        padded = (nbytes + 15) // 16 * 16 + 16
+        host = torch.zeros((padded,), dtype=torch.uint8)
+        if nbytes:
+            host[:nbytes] = torch.frombuffer(bytearray(buf), dtype=torch.uint8)
+        data = be.empty((padded,), torch.uint8)
+        data.copy_(host)
+        return cls.from_device(data, nbytes, final, be, host_text=buf)
+
+    @classmethod
+    def from_device(cls, data, nbytes, final=True, backend=None, host_text=None, unterminated=False):
+        """Index FASTA text that already sits in device memory (the conditions of ``FastqBatch.from_device``; the
+        tensor must be zero-padded to the next multiple of 16 and 16 bytes more).  Returns (batch, consumed)."""
+        be = backend or _lib.get_backend()
+        grown, records, record_ends, end, _nlines, err = be.fasta_index(data, nbytes)
+        if err != _lib.INT64_MAX:
+            if host_text is None:
+                host_text = bytes(data[:nbytes].cpu().numpy().tobytes())
+            cls._raise_format_error(host_text, err)
+        nrec, consumed = records.shape[0], nbytes
+        if not final:
+            nrec = max(nrec - 1, 0)
+            consumed = int(record_ends[nrec - 1].item()) + 1 if nrec else 0
+        return cls(grown, max(nbytes, end), records[:nrec], be, record_ends), consumed
+
+    @staticmethod
+    def _raise_format_error(buf, err):
+        """The reference's message for text in front of the first header (io/seqio.py:273-275)."""
+        line = _text(_universal_newlines(bytes(buf)).split(b"\n")[err // 8 - 1].strip(FASTA_SPACE))
+        shown = line if len(line) <= 100 else line[:97] + "..."             # util.truncate_string
+        raise FormatError("At line {0}: Expected '>' at beginning of FASTA record, but got {1!r}.".format(err // 8, shown))
+
+    def to_records(self, begin=None, end=None):
+        """Host copies [(name, sequence, None, ""), ...] -- test helper, not a product path."""
+        return [(name, seq, None, "") for name, seq, _, _ in FastqBatch.to_records(self, begin, end)]
+
+
 class RecordSource(object):
     """Read source of the device-resident adapter matchers (``Adapter.match_source``) over the
     kept intervals of a FastqBatch: packs ``sequence[begin:end]`` once per translate table."""
@@ -379,11 +511,18 @@ class ChunkedFastqReader(object):
 
     BGZF_SCAN = 4096                                         # members per bgzf_scan call
 
-    def __init__(self, path, chunk_bytes, backend=None, clock=None, byte_range=None, device_gunzip=False):
+    def __init__(self, path, chunk_bytes, backend=None, clock=None, byte_range=None, device_gunzip=False, input_format=None):
         name = str(path)
+        # "fasta" | "fastq": given, else by the file's name, else (None until the first chunk is there) by its first byte
+        self.fmt = input_format if input_format is not None else guess_format(name)
+        if self.fmt not in ("fasta", "fastq", None):
+            raise ValueError("input_format must be 'fasta' or 'fastq'")
+        if self.fmt == "fasta" and byte_range is not None:
+            raise NotImplementedError("a byte range of FASTA input is not provided")
         if byte_range is not None and name.endswith((".gz", ".bz2", ".xz")):
             raise ValueError("a byte range of compressed input: the offsets are those of the plain text")
         self.be = backend or _lib.get_backend()
+        self.byte_range = byte_range
         self.clock = clock or StageClock()
         self.chunk_bytes = int(chunk_bytes)
         cap = self.chunk_bytes + self.RESERVE
@@ -652,12 +791,22 @@ class ChunkedFastqReader(object):
                 ready.record()
         return nbytes, final, unterminated, data, ready, host
 
+    def _index(self, data, nbytes, unterminated, host=None):
+        """The batch of the chunk's whole records in the file's format (its first chunk decides an unknown one)."""
+        if self.fmt is None:
+            head = host[:min(nbytes, 1 << 16)] if host is not None else data[:min(nbytes, 1 << 16)].cpu()
+            self.fmt = sniff_format(head.numpy().tobytes())
+            if self.fmt == "fasta" and self.byte_range:
+                raise NotImplementedError("a byte range of FASTA input is not provided")
+        cls = FastaBatch if self.fmt == "fasta" else FastqBatch
+        return cls.from_device(data, nbytes, self.final, self.be, unterminated=unterminated)
+
     def next_batch(self):
-        """Upload and index the next chunk; returns the FastqBatch of its whole records."""
+        """Upload and index the next chunk; returns the FastqBatch (FastaBatch) of its whole records."""
         t0 = time.perf_counter()
         if self.bgzf:
             data, nbytes, unterminated = self._next_device()
-            batch, self.consumed = FastqBatch.from_device(data, nbytes, self.final, self.be, unterminated=unterminated)
+            batch, self.consumed = self._index(data, nbytes, unterminated)
             self.clock.add("upload_and_index", t0)
             return batch
         res = self.pending.result() if hasattr(self.pending, "result") else self.pending
@@ -675,7 +824,7 @@ class ChunkedFastqReader(object):
             with torch.cuda.device(self.be.device):
                 torch.cuda.current_stream().wait_event(ready)
                 data.record_stream(torch.cuda.current_stream())
-        batch, self.consumed = FastqBatch.from_device(data, nbytes, self.final, self.be, unterminated=unterminated)
+        batch, self.consumed = self._index(data, nbytes, unterminated, host)
         self.clock.add("upload_and_index", t0)
         return batch
 
@@ -723,7 +872,8 @@ class ChunkedFastqReader(object):
         self.buf = []
 
 
-def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, device_gunzip=False, interleaved=False):
+def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, device_gunzip=False, interleaved=False,
+                input_formats=None):
     """THE chunk loop of every file driver (trim, qc, error rate, detect, a rank's shard): yields a list of
     FastqBatch, one per path, chunk after chunk of whole records.  Several paths are read in lock step: every
     batch of a list holds the same number of records (the file whose chunk holds fewer decides, the surplus of the
@@ -740,7 +890,11 @@ def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, 
     odd number of records hands out all but the last, which is carried over like the surplus of a two-file run; an
     odd number of records in the whole file is the reference's FormatError (io/seqio.py:499-502).  The names of the
     two reads are not compared -- the two-file readers do not compare them either.  With ``byte_ranges`` it is a
-    ValueError: a range may begin at a read 2."""
+    ValueError: a range may begin at a read 2.
+
+    ``input_formats``: "fasta" | "fastq" | None per path; None is the file's name, else its first byte
+    (``input_format``).  FASTA paths yield ``FastaBatch``es; two paths of different formats are a ValueError, FASTA with
+    ``byte_ranges`` or ``interleaved`` a NotImplementedError."""
     mismatch = "the two input files hold different numbers of records"
     if interleaved:
         if len(paths) != 1:
@@ -749,10 +903,14 @@ def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, 
             raise ValueError("byte ranges of an interleaved file are not provided (a range may begin at a read 2)")
     readers = []
     try:
-        for path, byte_range in zip(paths, byte_ranges or [None] * len(paths)):
-            readers.append(ChunkedFastqReader(path, chunk_bytes, backend, clock, byte_range, device_gunzip))
+        for path, byte_range, fmt in zip(paths, byte_ranges or [None] * len(paths), input_formats or [None] * len(paths)):
+            readers.append(ChunkedFastqReader(path, chunk_bytes, backend, clock, byte_range, device_gunzip, fmt))
         while True:
             batches = [r.next_batch() for r in readers]
+            if len({r.fmt for r in readers}) > 1:
+                raise ValueError("the two input files are of different formats (%s)" % " and ".join(r.fmt for r in readers))
+            if interleaved and readers[0].fmt == "fasta":
+                raise NotImplementedError("interleaved FASTA input is not provided")
             if interleaved:
                 reader, batch = readers[0], batches[0]
                 if len(batch) % 2:

@@ -304,11 +304,18 @@ class PairedEndReadStatistics(object):
 
 # ---------------------------------------------------------------------------------------------- file drivers
 # (every chunk of ``fastq.read_chunks`` into the counters: one file, or two in lock step)
+def _need_qualities(batches):
+    """FASTA input has no qualities to count: a clear ValueError (the reference's qc and error commands fail on it)."""
+    if any(getattr(b, "fmt", "fastq") == "fasta" for b in batches):
+        raise ValueError("read statistics and error rates need quality values: the input is FASTA")
+
+
 def qc_file(path, chunk_bytes=64 << 20, quality_base=33, qualities=True, device_gunzip=False):
     """``atropos qc`` of one FASTQ file: {"pre": {0: {"read1": summary}}} (QcPipeline.finish).  ``device_gunzip``
     (here and in the drivers below): BGZF ``.gz`` input is inflated on the GPU (``fastq.ChunkedFastqReader``)."""
     st = SingleEndReadStatistics(qualities=qualities, quality_base=quality_base)
     for batches in read_chunks([path], chunk_bytes, device_gunzip=device_gunzip):
+        _need_qualities(batches)
         st.collect_batch(*batches)
     return {"pre": {0: st.summarize()}}
 
@@ -319,6 +326,7 @@ def qc_files(path1, path2=None, chunk_bytes=64 << 20, quality_base=33, qualities
     st = PairedEndReadStatistics(qualities=qualities, quality_base=quality_base)
     paths = [path1] if path2 is None else [path1, path2]
     for batches in read_chunks(paths, chunk_bytes, device_gunzip=device_gunzip, interleaved=path2 is None):
+        _need_qualities(batches)
         st.collect_batch(*batches)
     return {"pre": {0: st.summarize()}}
 
@@ -332,6 +340,7 @@ def error_rate_file(path, path2=None, max_bases=None, chunk_bytes=64 << 20, devi
     paths = [path] if path2 is None else [path, path2]
     sts = [ReadStatistics(qualities=True) for _ in range(2 if interleaved else len(paths))]
     for batches in read_chunks(paths, chunk_bytes, device_gunzip=device_gunzip, interleaved=interleaved):
+        _need_qualities(batches)
         for st, batch in zip(sts, batches):
             st.collect_batch(batch)
     res = [s.error_rate(max_bases) for s in sts]

@@ -38,7 +38,8 @@ import torch
 from . import _lib
 from .adapters import LinkedAdapter
 from .report import SLOT_CUT, SLOT_MINCUT, SLOT_NEND, SLOT_NEXTSEQ, SLOT_QUALITY, TrimReport, check_envelope
-from .fastq import FastqBatch, RecordSource, StageClock, make_sink, open_by_extension, read_chunks
+from .fastq import (FastaBatch, FastqBatch, RecordSource, StageClock, guess_format, input_format, make_sink, open_by_extension,
+                    read_chunks, sniff_format)
 
 DEST_MERGED = 6              # MergedReadFilter (filters.py:109-113): installed first, so a merged pair goes nowhere else
 DEST_NAMES = {_lib.DEST_KEEP: "keep", _lib.DEST_TOO_SHORT: "too_short", _lib.DEST_TOO_LONG: "too_long",
@@ -155,6 +156,7 @@ class TrimResult(object):
         # a demultiplexed run (TrimPipeline(demultiplex=True)): the output code of every read (int32, -1: not written
         # here) and the outputs' names -- the adapters' names, then "unknown" for the untrimmed output if there is one
         self.group, self.group_names = None, None
+        self.fmt = getattr(batch, "fmt", "fastq")               # what ``text`` writes by default: "fasta" over a FastaBatch
 
     def aux_text(self, kinds=("info", "rest", "wildcard")):
         """The lines the reference's InfoFormatter / RestFormatter / WildcardFormatter write for this batch
@@ -237,12 +239,82 @@ class TrimResult(object):
                 out[name] = out.get(name, b"") + host[edges[g]:edges[g + 1]].tobytes()
         return out
 
-    def text(self, which=_lib.DEST_KEEP):
-        """Formatted FASTQ text (bytes) of the reads sent to destination ``which``."""
+    def text(self, which=_lib.DEST_KEEP, fmt=None):
+        """Formatted text (bytes) of the reads sent to destination ``which``: ``fmt`` = "fastq" | "fasta", by default
+        the format the batch was read from.  FASTQ of a FASTA batch is the reference's ValueError."""
         be = self.batch.backend
-        out = be.fastq_emit(self.batch.data, self.batch.records, self.begin, self.end, self.ubegin, self.uend,
-                            self.dest, which)
+        fmt = fmt or self.fmt
+        if fmt == "fastq" and self.fmt == "fasta":
+            raise ValueError(NO_QUALITIES)
+        emit = be.fasta_emit if fmt == "fasta" else be.fastq_emit
+        out = emit(self.batch.data, self.batch.records, self.begin, self.end, self.ubegin, self.uend, self.dest, which)
         return bytes(out.cpu().numpy().tobytes())
+
+
+NO_QUALITIES = "Output format cannot be FASTQ since no quality values are available."     # io/seqio.py:1053-1056
+
+
+def output_format(path, fasta_input):
+    """"fasta" | "fastq" for one output path, as the reference's ``get_format`` (io/seqio.py:1008-1067): by the path's
+    own name; a name that says nothing gets FASTA when the input has no qualities and FASTQ otherwise; FASTQ by name
+    for reads without qualities is its ValueError."""
+    fmt = guess_format(path) or ("fasta" if fasta_input else "fastq")
+    if fmt == "fastq" and fasta_input:
+        raise ValueError(NO_QUALITIES)
+    return fmt
+
+
+def refuse_for_fasta(pipe):
+    """What a pipeline cannot do with reads that have no qualities: the options the reference crashes on or needs
+    qualities for are a ValueError naming the option, what is out of scope a NotImplementedError."""
+    paired = _is_paired(pipe)
+    first = pipe.p1 if paired else pipe
+    second = getattr(pipe, "p2", None)
+    pipes = [first] + ([second] if second is not None else [])
+    for given, option in ((any(p.quality_cutoff for p in pipes), "-q / --quality-cutoff"),
+                          (any(p.nextseq_trim is not None for p in pipes), "--nextseq-trim"),
+                          (getattr(pipe, "overwrite_low_quality", None), "-w / --overwrite-low-quality"),
+                          (pipe.stats, "--stats"),
+                          (getattr(pipe, "correct_mismatches", None), "--correct-mismatches"),
+                          (getattr(pipe, "merge_overlapping", False), "-R / --merge-overlapping")):
+        if given:
+            raise ValueError("%s needs quality values: the input is FASTA" % option)
+    if pipe.report:
+        raise NotImplementedError("report=True with FASTA input")
+    if getattr(pipe, "demultiplex", False):
+        raise NotImplementedError("demultiplexing ({name} in the output path) with FASTA input")
+
+
+class TrimFormats(object):
+    """The formats of one file run, settled before any output is opened: ``inputs`` (one per input path, all the
+    same), ``outputs`` (one per main output path) and ``dests`` ({destination code: one per path} of the too-short /
+    too-long / untrimmed files)."""
+
+    def __init__(self, pipe, paths_in, paths_out, merged_out=None, byte_ranges=None, explicit=None):
+        self.inputs = [input_format(p, explicit) for p in paths_in]
+        if len(set(self.inputs)) > 1:
+            raise ValueError("the two input files are of different formats (%s)" % " and ".join(self.inputs))
+        self.fasta = fasta = self.inputs[0] == "fasta"
+        paired = _is_paired(pipe)
+        demux = pipe_demultiplexes(pipe, paths_out, merged_out)
+        if fasta:
+            refuse_for_fasta(pipe)
+            if demux:
+                raise NotImplementedError("demultiplexing ({name} in the output path) with FASTA input")
+            if paired and (len(paths_in) == 1 or len(paths_out) == 1):
+                raise NotImplementedError("interleaved FASTA input / output (-l / -L) is not provided")
+            if byte_ranges is not None and any(r is not None for r in byte_ranges):
+                raise NotImplementedError("a byte range of FASTA input is not provided")
+        self.outputs = [output_format(p, fasta) for p in paths_out]
+        if merged_out is not None:
+            self.outputs_merged = output_format(merged_out, fasta)
+        codes = {name: code for code, name in DEST_NAMES.items()}
+        self.dests = {codes[kind]: [output_format(p, fasta) for p in (paths if paired else (paths,))]
+                      for kind, paths in pipe.outputs.items()}
+        if "fasta" in self.outputs or (merged_out is not None and self.outputs_merged == "fasta"):
+            # FASTQ reads into a FASTA-named file: the plain formatter does it, the grouped / pair / merge ones do not
+            if demux or (paired and len(paths_out) == 1) or (merged_out is not None and self.outputs_merged == "fasta"):
+                raise NotImplementedError("FASTA output of demultiplexed, interleaved or merged reads is not provided")
 
 
 class _Mate(object):
@@ -298,8 +370,18 @@ def _run_stages(pipes, mates, insert_stage=None, overwrite_stage=None):
     return found
 
 
+def _batch_from_bytes(pipe, data, explicit=None):
+    """The one batch of ``trim_bytes``: a FastaBatch if the text is FASTA (and the pipeline takes FASTA)."""
+    if explicit not in (None, "fasta", "fastq"):
+        raise ValueError("input_format must be 'fasta' or 'fastq'")
+    if (explicit or sniff_format(bytes(data[:1 << 16]))) == "fasta":
+        refuse_for_fasta(pipe)
+        return FastaBatch.from_bytes(data, final=True)[0]
+    return FastqBatch.from_bytes(data, final=True)[0]
+
+
 def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out=None, byte_ranges=None,
-                 device_gzip=False, device_gunzip=False):
+                 device_gzip=False, device_gunzip=False, input_format=None):
     """What ``TrimPipeline.trim_file`` (one input), ``PairedTrimPipeline.trim_files`` (two inputs in lock step, or one
     interleaved input) and ``shard.sharded_trim_file`` (``byte_ranges``: a rank's part of the input) do with every
     chunk of ``fastq.read_chunks``; returns the destination counts.  A paired pipeline with ONE input path reads it as
@@ -316,15 +398,17 @@ def _trim_stream(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
         for p in list(paths_out) + ([merged_out] if merged_out is not None else []):
             if not str(p).endswith(".gz"):
                 raise ValueError("device_gzip: the output path must end in .gz (%r)" % str(p))
+    # FASTA or FASTQ, per input and per output (by explicit format, name, first byte): refusals come before any file
+    formats = TrimFormats(pipe, paths_in, paths_out, merged_out, byte_ranges, input_format)
     if not pipe.report:
         return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, None,
-                            device_gzip, device_gunzip)
+                            device_gzip, device_gunzip, formats)
     # the report's counters: made before any output is opened (the table bound refuses here), on the device until the
     # file is done
     report = TrimReport(pipe, source=tuple(paths_in) if len(paths_in) == 2 else paths_in[0])
     try:
         return _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report,
-                            device_gzip, device_gunzip)
+                            device_gzip, device_gunzip, formats)
     finally:
         report.close()
 
@@ -340,10 +424,12 @@ def pipe_demultiplexes(pipe, paths_out, merged_out=None):
 
 
 def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_parts, merged_out, byte_ranges, report,
-                 device_gzip=False, device_gunzip=False):
+                 device_gzip=False, device_gunzip=False, formats=None):
     """The chunk loop of ``_trim_stream``; ``report``: the run's TrimReport or None; ``device_gzip``: the main
     outputs and the merged output through ``fastq.DeviceGzipSink`` (side files stay on the host path);
-    ``device_gunzip``: BGZF ``.gz`` input inflated on the GPU (``fastq.ChunkedFastqReader``)."""
+    ``device_gunzip``: BGZF ``.gz`` input inflated on the GPU (``fastq.ChunkedFastqReader``); ``formats``: the run's
+    ``TrimFormats``."""
+    formats = formats or TrimFormats(pipe, paths_in, paths_out, merged_out, byte_ranges)
     paired = _is_paired(pipe)
     interleaved_in = paired and len(paths_in) == 1
     interleaved_out = paired and len(paths_out) == 1
@@ -351,6 +437,7 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
     merging = paired and pipe.merge_overlapping
     TrimStats.check(pipe.stats, first.discard_trimmed, first.discard_untrimmed, merging)
     be = _lib.get_backend()
+    emitters = [be.fasta_emit if fmt == "fasta" else be.fastq_emit for fmt in formats.outputs]    # (one per main output)
     totals = {name: 0 for name in DEST_NAMES.values()}
     clock = StageClock()
     demux = not paired and pipe.demultiplex
@@ -379,7 +466,8 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
                                     device_gzip=device_gzip)
     stats = TrimStats(pipe.stats, paired, first.quality_base) if pipe.stats else None
     try:
-        for batches in read_chunks(paths_in, chunk_bytes, be, clock, byte_ranges, device_gunzip, interleaved=interleaved_in):
+        for batches in read_chunks(paths_in, chunk_bytes, be, clock, byte_ranges, device_gunzip, interleaved=interleaved_in,
+                                   input_formats=formats.inputs):
             t0 = time.perf_counter()
             if stats is not None and stats.pre is not None:
                 stats.pre.collect_batch(*batches)             # before any stage writes into the chunks
@@ -393,8 +481,8 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
             elif interleaved_out:
                 texts = [res.device_text_interleaved(_lib.DEST_KEEP)]
             else:
-                texts = [be.fastq_emit(r.batch.data, r.batch.records, r.begin, r.end, r.ubegin, r.uend, r.dest,
-                                       _lib.DEST_KEEP) for r in reads]
+                texts = [emit(r.batch.data, r.batch.records, r.begin, r.end, r.ubegin, r.uend, r.dest, _lib.DEST_KEEP)
+                         for emit, r in zip(emitters, reads)]
             counts = res.counts()
             if report is not None:
                 report.add(res)
@@ -419,8 +507,8 @@ def _trim_chunks(pipe, paths_in, paths_out, chunk_bytes, keep_output, output_par
                 for kind, blob in res.aux_text(tuple(aux_files)).items():
                     aux_files[kind].write(blob)
             for code, fhs in dest_files.items():              # the filtered reads that have a file of their own
-                for fh, r in zip(fhs, reads):
-                    fh.write(r.text(code))
+                for fh, r, fmt in zip(fhs, reads, formats.dests[code]):
+                    fh.write(r.text(code, fmt))
             for name, v in counts.items():
                 totals[name] += v
         if stats is not None:
@@ -757,13 +845,15 @@ class TrimPipeline(object):
     def _result(self, m, dest):
         """The tail of a run: the zero cap and the read-name modifiers, then the TrimResult of the mate."""
         b, n = m.batch, len(m.batch)
-        if self.zero_cap and n:
+        fmt = getattr(b, "fmt", "fastq")
+        if self.zero_cap and n and fmt != "fasta":              # (no qualities: the reference does not install ZeroCapper)
             if m.rounds is not None and m.unmasked is None:        # a match's info record shows the read as the match saw it:
                 m.unmasked = b.data.clone()                        # before ZeroCapper (align/__init__.py:145-170)
             self._zero_cap(m)
         read_batch = b if m.unmasked is None else FastqBatch(m.unmasked, b.nbytes, b.records, b.backend, b.line_ends)
         batch = self._rewrite_names(m) if self._name_mods and n else b
         res = TrimResult(batch, m.begin, m.end, m.ubegin, m.uend, m.matched, dest, m.rounds, self.adapters, read_batch)
+        res.fmt = fmt
         if self.demultiplex:
             names, adapter_group, untrimmed = self._demux_groups()
             table = torch.tensor(adapter_group or [0], dtype=torch.int32, device=dest.device)
@@ -830,13 +920,13 @@ class TrimPipeline(object):
         records = torch.from_numpy(recs.astype(np.int32)).to(batch.records.device)
         return FastqBatch(data, batch.nbytes, records, batch.backend, batch.line_ends)
 
-    def trim_bytes(self, data, which=_lib.DEST_KEEP):
-        """FASTQ text in, trimmed FASTQ text out (one batch)."""
-        batch, _ = FastqBatch.from_bytes(data, final=True)
-        return self.run(batch).text(which)
+    def trim_bytes(self, data, which=_lib.DEST_KEEP, input_format=None, fmt=None):
+        """FASTQ (FASTA) text in, trimmed text out (one batch).  ``input_format``: "fastq" | "fasta", by default what
+        the first byte says (``fastq.sniff_format``); ``fmt``: the output's, by default the input's."""
+        return self.run(_batch_from_bytes(self, data, input_format)).text(which, fmt)
 
     def trim_file(self, path_in, path_out, chunk_bytes=256 << 20, keep_output=False, output_parts=1, device_gzip=False,
-                  device_gunzip=False):
+                  device_gunzip=False, input_format=None):
         """Stream a FASTQ file through the GPU in chunks of whole records; returns the
         destination counts.  (Plain files; compressed input is the caller's business.)
         Host side: ``fastq.read_chunks`` (the one chunk loop, over ``ChunkedFastqReader``) / ``FastqSink`` (page-locked staging buffers, threaded
@@ -861,12 +951,18 @@ class TrimPipeline(object):
         ``device_gunzip``: a ``path_in`` that ends in ``.gz`` and holds BGZF members (``bgzip``, htslib,
         ``device_gzip=True``) is inflated on the GPU, a wave per member, instead of by one host thread; any other
         input is read as without the flag (``fastq.ChunkedFastqReader``).  It only changes where the text comes
-        from, and combines with every other option."""
+        from, and combines with every other option.
+
+        FASTA: the input is read as FASTA when ``input_format`` = "fasta", else when its name ends in .fasta / .fa /
+        .fna (a compression suffix aside), else when its first byte is '>' (``fastq.input_format``).  The output is
+        FASTA when its name says so, FASTQ when its name says so, and what the input is otherwise (``output_format``);
+        the same goes for the too-short / too-long / untrimmed files.  FASTA input into a FASTQ-named file, and the
+        options that need qualities (``refuse_for_fasta``), are refused before any file is opened."""
         if device_gzip and ("{name}" in path_out or self.demultiplex):
             raise NotImplementedError("device_gzip with demultiplexed outputs ({name} in the output path)")
         if "{name}" not in path_out and not self.demultiplex:
             return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts, device_gzip=device_gzip,
-                                device_gunzip=device_gunzip)
+                                device_gunzip=device_gunzip, input_format=input_format)
         if "{name}" not in path_out:
             raise ValueError("a demultiplexing pipeline needs {name} in the output path")
         if output_parts and int(output_parts) > 1:
@@ -875,7 +971,8 @@ class TrimPipeline(object):
         self.demultiplex = True
         try:
             self._check_demux()                               # before any output is opened
-            return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts, device_gunzip=device_gunzip)
+            return _trim_stream(self, [path_in], [path_out], chunk_bytes, keep_output, output_parts, device_gunzip=device_gunzip,
+                                input_format=input_format)
         finally:
             self.demultiplex = was
 
@@ -907,8 +1004,8 @@ class PairedTrimResult(object):
         """FASTQ text of the merged reads (the --merged-output file), in input order."""
         return b"" if self.merged is None else bytes(self.merged.cpu().numpy().tobytes())
 
-    def text(self, which=_lib.DEST_KEEP):
-        return self.read1.text(which), self.read2.text(which)
+    def text(self, which=_lib.DEST_KEEP, fmt=None):
+        return self.read1.text(which, fmt), self.read2.text(which, fmt)
 
     def device_text_interleaved(self, which=_lib.DEST_KEEP):
         """``text_interleaved`` as a uint8 device tensor (one ``atr_fastq_emit_pairs``)."""
@@ -1251,7 +1348,7 @@ class PairedTrimPipeline(object):
         return PairedTrimResult(self.p1._result(mates[0], dest), self.p2._result(mates[1], dest), merged_text)
 
     def trim_files(self, in1, in2, out1, out2=None, chunk_bytes=128 << 20, merged_out=None, keep_output=False, output_parts=1,
-                   device_gzip=False, device_gunzip=False):
+                   device_gzip=False, device_gunzip=False, input_format=None):
         """Stream two FASTQ files through the GPU in lock step (chunks of whole records, the
         same number from each file); returns the destination counts.
 
@@ -1268,19 +1365,24 @@ class PairedTrimPipeline(object):
         ``output_parts`` > 1: every output as that many part files (``TrimPipeline.trim_file``); part i of
         ``out1`` and part i of ``out2`` hold the same pairs in the same order.  ``device_gzip``: the outputs
         (all ending in ``.gz``) are compressed on the GPU, as in ``TrimPipeline.trim_file``.  ``device_gunzip``: BGZF
-        ``.gz`` inputs are inflated on the GPU, as in ``TrimPipeline.trim_file``."""
+        ``.gz`` inputs are inflated on the GPU, as in ``TrimPipeline.trim_file``.  FASTA input and output, and
+        ``input_format``, as in ``TrimPipeline.trim_file``; both inputs are of one format, interleaved FASTA is a
+        NotImplementedError."""
         if device_gzip and any(p is not None and "{name}" in str(p) for p in (out1, out2, merged_out)):
             raise NotImplementedError("device_gzip with demultiplexed outputs ({name} in the output path)")
         if any(p is not None and "{name}" in str(p) for p in (out1, out2, merged_out)):
             raise ValueError("Demultiplexing not supported for paired-end files, yet.")        # trim/cli.py:769-771
         return _trim_stream(self, [in1] if in2 is None else [in1, in2], [out1] if out2 is None else [out1, out2], chunk_bytes,
-                            keep_output, output_parts, merged_out, device_gzip=device_gzip, device_gunzip=device_gunzip)
+                            keep_output, output_parts, merged_out, device_gzip=device_gzip, device_gunzip=device_gunzip,
+                            input_format=input_format)
 
-    def trim_bytes(self, data1, data2, which=_lib.DEST_KEEP):
-        """Two FASTQ texts in (same number of records), the two trimmed texts out."""
-        b1, _ = FastqBatch.from_bytes(data1, final=True)
-        b2, _ = FastqBatch.from_bytes(data2, final=True)
-        return self.run(b1, b2).text(which)
+    def trim_bytes(self, data1, data2, which=_lib.DEST_KEEP, input_format=None, fmt=None):
+        """Two FASTQ (FASTA) texts in (same number of records, one format), the two trimmed texts out; ``input_format``
+        and ``fmt`` as in ``TrimPipeline.trim_bytes``."""
+        b1, b2 = _batch_from_bytes(self, data1, input_format), _batch_from_bytes(self, data2, input_format)
+        if getattr(b1, "fmt", "fastq") != getattr(b2, "fmt", "fastq"):
+            raise ValueError("the two inputs are of different formats")
+        return self.run(b1, b2).text(which, fmt)
 
 
 class LegacyPairedPipeline(PairedTrimPipeline):

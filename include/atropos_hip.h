@@ -945,6 +945,48 @@ int atr_bgzf_scan(const uint8_t *buf, int64_t n_bytes, int64_t max_members, int6
 int atr_gunzip_members(const uint8_t *d_stream, int64_t n_stream, const int64_t *d_member_at, const int64_t *d_text_at,
                        int64_t n_members, uint8_t *d_text, int64_t text_capacity, int32_t *d_status, int32_t *d_bad, void *stream);
 
+/* ---- device-resident FASTA batch -------------------------------------------------------------
+ * The reference's FastaReader (io/seqio.py:233-280) over a chunk of text in device memory, under the
+ * conditions of atr_fastq_index: below 4 GiB, 16-byte aligned, readable up to the next multiple of 16
+ * plus one byte, ending in a line end, starting at a header or at the top of the file.  Every line is
+ * stripped of the ASCII whitespace " \t\n\r\x0b\x0c\x1c\x1d\x1e\x1f" (bytes >= 0x80 never count),
+ * blank lines and lines that start with '#' are skipped, a line that starts with '>' opens a record.
+ * Line ends are Python's universal newlines, as in atr_fastq_index, and the lines are counted by the same call:
+ *
+ *   atr_fastq_count_lines  nlines, as for FASTQ.
+ *   atr_fasta_scan         d_line_ends[nlines]; d_info[0] = records (header lines), d_info[1] = bytes that
+ *                          need unwrapping (the sequence lengths of all records with more than one sequence
+ *                          line), d_info[2] = line_number * 8 + ATR_FASTA_ERR_HEADER of the first line that
+ *                          is neither skipped nor a header in front of the first header (line_number from
+ *                          1, skipped lines count), INT64_MAX if there is none.  d_work: scratch of
+ *                          atr_fasta_work_bytes(nbytes, nlines) bytes (not the count's), handed unchanged to
+ *                          atr_fasta_index.
+ *   atr_fasta_index        one atr_fastq_record per record: name = the stripped header after '>';
+ *                          the sequence is the single stripped sequence line in place if there is at most
+ *                          one, else the record's lines gathered at d_bytes[tail_off ...] (tail_off: a
+ *                          multiple of 16 at or beyond nbytes; tail_bytes: the room there, at least
+ *                          d_info[1]; tail_off + tail_bytes below 4 GiB); qual_off = qual_len = flags = 0.
+ *                          d_record_ends[r]: the last byte of the line end of the record's last line.
+ *
+ * No global atomics take part in the sums: equal input gives equal descriptors and an equal tail. */
+#define ATR_FASTA_ERR_HEADER 1
+size_t atr_fasta_work_bytes(int64_t nbytes, int64_t nlines);
+int atr_fasta_scan(const uint8_t *d_bytes, int64_t nbytes, uint32_t *d_line_ends, int64_t nlines, void *d_work,
+                   int64_t *d_info, void *stream);
+int atr_fasta_index(uint8_t *d_bytes, int64_t nbytes, const uint32_t *d_line_ends, int64_t nlines, const void *d_work,
+                    int64_t nrec, int64_t tail_off, int64_t tail_bytes, atr_fastq_record *d_records,
+                    uint32_t *d_record_ends, void *stream);
+
+/* FastaFormat (io/seqio.py:1008-1067, never wrapped): '>' name '\n' sequence[begin:end] '\n' of every
+ * record with d_dest[r] == dest, in input order.  Arguments and the two-call protocol of atr_fastq_emit;
+ * bases outside the unmasked interval read 'N'.  Only name_off / name_len / seq_off are read, so a
+ * FASTQ batch (and a record whose name was re-pointed) is formatted as well. */
+size_t atr_fasta_emit_work_bytes(int64_t n);
+int atr_fasta_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, const int32_t *d_begin,
+                   const int32_t *d_end, const int32_t *d_unmasked_begin, const int32_t *d_unmasked_end,
+                   const uint8_t *d_dest, int dest, int64_t n, int record_bytes_hint, int64_t *d_offsets, void *d_work,
+                   uint8_t *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
