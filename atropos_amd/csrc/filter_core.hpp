@@ -266,6 +266,12 @@ inline FilterParams filter_params(const uint64_t *peq64, const uint8_t *codes, i
 //   [28] band: only row-m candidates, all of them inside BAND_W diagonals from j_lo on
 //   [31] valid (needs the DP)
 constexpr int BAND_W = 16;
+// Row-m band reads get the intersection of the hits' band and the pieces' band (filter_decide_tm).  0 (the run-time
+// compiled kernel: ATR_SPEC_FLAGS=-DATR_BAND_INTERSECT=0): the hits' band alone, the pieces' one where that does not
+// fit -- for A/B.
+#ifndef ATR_BAND_INTERSECT
+#define ATR_BAND_INTERSECT 1
+#endif
 ATR_DEV uint32_t window_word(int j_lo, int j_hi, bool scan, int rows, bool band) {
     return 0x80000000u | (uint32_t)j_lo | ((uint32_t)j_hi << 10) | (scan ? (1u << 20) : 0u) | ((uint32_t)rows << 21) |
            (band ? (1u << 28) : 0u);
@@ -642,7 +648,9 @@ struct FilterNoDiag { ATR_DEV_MEMBER uint64_t operator()(int) const { return ~0u
 // diagonal of its intact piece by at most its indels <= k: d_min - k .. d_max + k (the caller hands over max(0, d_min - k):
 // a first diagonal of 0 may be a clamped one -- cells below the main diagonal exist -- and is not taken).  The hits of the swept rows spread
 // over 2 (k - c) more columns than that (every column within k - c of a cost-c occurrence is a hit), which for k >= 5
-// pushed every read with an error out of the 16-diagonal band into the column window (64-mers: 1.6 of 2.1 ms).
+// pushed every read with an error out of the 16-diagonal band into the column window (64-mers: 1.6 of 2.1 ms).  Where both
+// bands are valid the read gets their intersection: on C2 the row-m band reads then sweep 8.8 diagonals in the mean (the
+// ND variant of band_locate their width selects), not 11.7.
 template <bool WIDE, class P, class TM, class DG = FilterNoDiag>
 ATR_DEV uint32_t filter_decide_tm(const FilterState &F, const Uniform &u, const P &fp, TM tm, int n, uint32_t rec[4],
                                   int s = 0, bool have_last = true, DG dg = DG(), int pa_dlo = 0, int pa_dhi = -1) {
@@ -739,7 +747,8 @@ ATR_DEV uint32_t filter_decide_tm(const FilterState &F, const Uniform &u, const 
     bool band = rowm && !lastcol && (F.j_first - mf - u.k >= s) &&
                 (F.j_last - F.j_first + 2 * u.k <= BAND_W - 1);
     int band_hi = F.j_last + T;
-    if (!band && rowm && !lastcol && !u.sr && pa_dhi >= pa_dlo && pa_dlo > s && pa_dhi - pa_dlo <= BAND_W - 1) {
+    const bool pa = rowm && !lastcol && !u.sr && pa_dhi >= pa_dlo && pa_dlo > s;
+    if (!band && pa && pa_dhi - pa_dlo <= BAND_W - 1) {
         band = true;                                                     // the pieces' diagonals (see above)
         j_lo = pa_dlo;
         band_hi = pa_dhi + u.m - u.k;
@@ -759,6 +768,13 @@ ATR_DEV uint32_t filter_decide_tm(const FilterState &F, const Uniform &u, const 
                 return 0;
             }
         }
+    }
+    if (ATR_BAND_INTERSECT && band && pa) {
+        // BOTH bands hold every path of cost <= k to a row-m candidate (the hits': see above, its first diagonal whenever it is
+        // not clamped; the pieces': at filter_decide_tm), so their intersection does.  A swept-row hit need not belong to an
+        // alignment of all m rows (NARROW mode): an empty intersection is left alone.
+        const int lo = atr_max(pa_dlo, F.j_first - mf - u.k), hi = atr_min(pa_dhi + u.m - u.k, F.j_last + T);
+        if (hi - (u.m - u.k) >= lo) { j_lo = lo; band_hi = hi; }
     }
     const int j_hi = lastcol ? n : band ? band_hi : atr_min(n, F.j_last + (T ? T + u.k : 0));
     // rows: with a row-m candidate all m rows; otherwise nothing above the largest acceptable

@@ -48,6 +48,14 @@
 #ifndef ATR_PIECE_OVERLAP_A
 #define ATR_PIECE_OVERLAP_A 1
 #endif
+// the run-time compiled pass A keeps two code planes and one base mask where the generic one keeps four base masks
+// (piece_scan_spec); 0: the four masks (ATR_SPEC_FLAGS=-DATR_PIECE_TWO_PLANES=0)
+#ifndef ATR_PIECE_TWO_PLANES
+#define ATR_PIECE_TWO_PLANES 1
+#endif
+#ifndef ATR_SPEC_RAGGED
+#define ATR_SPEC_RAGGED 0
+#endif
 
 namespace atr {
 
@@ -828,8 +836,61 @@ ATR_DEV PieceScan piece_scan(const PieceParams &pp, const uint32_t (&pl)[NW][4],
 // (s_bitcmp1 + branch per term: 40 % of its issue time) are gone, as are the ~700 bytes of kernel
 // argument that kept 116 SGPRs spilled.
 template <int V> struct PieceIC { static constexpr int value = V; };
+// Every term of the straight-line pass A is a volatile one-instruction asm, in source order: left to itself the scheduler
+// moves the ands of a step behind the in-place shift that follows them, keeps copies of every older mask and spills a
+// hundred registers (round 5, first try).  In this order the live set is the masks + occ + tocc.
+ATR_DEV void piece_asm_and(uint32_t &acc, uint32_t y) {
+#ifdef ATR_HOST_EMU
+    acc &= y;
+#else
+    asm volatile("v_and_b32 %0, %0, %1" : "+v"(acc) : "v"(y));
+#endif
+}
+// bit i of TBL = the result where (a, b, c) = (i >> 2 & 1, i >> 1 & 1, i & 1)
+ATR_DEV uint32_t piece_bitop3_host(int tbl, uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r = 0u;
+    for (int i = 0; i < 8; ++i)
+        if ((tbl >> i) & 1) r |= ((i & 4) ? a : ~a) & ((i & 2) ? b : ~b) & ((i & 1) ? c : ~c);
+    return r;
+}
+template <int TBL>
+ATR_DEV uint32_t piece_bitop3(uint32_t a, uint32_t b, uint32_t c) {
+#ifdef ATR_HOST_EMU
+    return piece_bitop3_host(TBL, a, b, c);
+#else
+    uint32_t r;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:%4" : "=v"(r) : "v"(a), "v"(b), "v"(c), "n"(TBL));
+    return r;
+#endif
+}
+// one word of three masks one position up: FIRST starts the three carry chains (scalar register pairs), the others
+// take the carry of the word below and leave their own
+template <bool FIRST>
+ATR_DEV void piece_shift3(uint32_t &h, uint32_t &l, uint32_t &y, uint64_t &ch, uint64_t &cl, uint64_t &cy) {
+#ifdef ATR_HOST_EMU
+    if (FIRST) ch = cl = cy = 0;
+    const uint32_t vh = h, vl = l, vy = y;
+    h = (vh << 1) | (uint32_t)ch; l = (vl << 1) | (uint32_t)cl; y = (vy << 1) | (uint32_t)cy;
+    ch = vh >> 31; cl = vl >> 31; cy = vy >> 31;
+#else
+    if constexpr (FIRST)
+        asm volatile("v_add_co_u32 %0, %3, %0, %0\n\tv_add_co_u32 %1, %4, %1, %1\n\tv_add_co_u32 %2, %5, %2, %2"
+                     : "+v"(h), "+v"(l), "+v"(y), "=&s"(ch), "=&s"(cl), "=&s"(cy));
+    else
+        asm volatile("v_addc_co_u32 %0, %3, %0, %0, %3\n\tv_addc_co_u32 %1, %4, %1, %1, %4\n\tv_addc_co_u32 %2, %5, %2, %2, %5"
+                     : "+v"(h), "+v"(l), "+v"(y), "+s"(ch), "+s"(cl), "+s"(cy));
+#endif
+}
+template <int TBL>
+ATR_DEV void piece_asm_bitop3(uint32_t &acc, uint32_t h, uint32_t l) {       // acc = TBL(acc, h, l), in place and in source order
+#ifdef ATR_HOST_EMU
+    acc = piece_bitop3_host(TBL, acc, h, l);
+#else
+    asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:%3" : "+v"(acc) : "v"(h), "v"(l), "n"(TBL));
+#endif
+}
 template <int I, int N, class F>
-__device__ __forceinline__ void piece_static_for(F &&f) {
+ATR_DEV void piece_static_for(F &&f) {
     if constexpr (I < N) { f(PieceIC<I>{}); piece_static_for<I + 1, N>(f); }
 }
 
@@ -839,8 +900,31 @@ ATR_DEV PieceScan piece_scan_spec(const uint32_t (&pl)[NW][4], const uint32_t (&
     constexpr int TWN = NW < PIECE_TAIL_WORDS ? NW : PIECE_TAIL_WORDS, TW0 = NW - TWN;
     constexpr int HWN = NW < PIECE_HEAD_WORDS ? NW : PIECE_HEAD_WORDS;
     constexpr int n = spec::N;
+    // TWO CODE PLANES AND ONE BASE MASK (ATR_PIECE_TWO_PLANES; one-hot codes, equal-length batches).  With one-hot planes
+    // H = p2 | p3 and L = p1 | p3 name the base, and acc &= [base == c] is ONE three-input op on (acc, H, L) -- so only H
+    // and L need the per-step shift, not four masks.  The minterm of code 0 (H = L = 0) would also hold wherever there is
+    // no base at all: N and multi-plane codes, positions >= n of the last word, the zeros a shift brings in below
+    // position 0.  Code 0 therefore keeps its own mask Y0 = "plane 0 and no other", and H and L are cleared where not
+    // exactly one plane is set: such a position then reads (H, L, Y0) = (0, 0, 0) and matches NO code, as it does in all
+    // four masks of piece_eq_masks.  Position by position [Y0, ~H & L, H & ~L, H & L] = Y[0 .. 3] before and after every
+    // shift, so occ, tocc and all that follows are the four-mask form's bit for bit -- no superset, no guard on j_exact.
+    // Three carry chains a step instead of four (15 instead of 20 ops at NW = 5, nine steps a tile), five registers fewer.
+    constexpr bool TWO = ATR_PIECE_TWO_PLANES != 0 && spec::PP.and_mode == 0 && ATR_SPEC_RAGGED == 0;
     PieceMasks<NW> Y;
-    piece_eq_masks<NW>(pl, spec::PP.and_mode != 0, Y);
+    uint32_t H[NW], L[NW], Y0[NW];
+    if constexpr (TWO) {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const uint32_t p0 = pl[w][0], p1 = pl[w][1], p2 = pl[w][2], p3 = pl[w][3];
+            const uint32_t u = piece_bitop3<0x16>(p0, p1, p2), z = piece_bitop3<0x01>(p0, p1, p2);   // exactly one / none of the three
+            const uint32_t one = piece_bitop3<0xD8>(u, z, p3);                                       // (u & ~p3) | (z & p3)
+            H[w] = piece_bitop3<0xA8>(p2, p3, one);                                                  // (p2 | p3) & one
+            L[w] = piece_bitop3<0xA8>(p1, p3, one);
+            Y0[w] = p0 & one;
+        }
+    } else {
+        piece_eq_masks<NW>(pl, spec::PP.and_mode != 0, Y);
+    }
 
     // (0) START_WITHIN_SEQ1: the read-start conditions (piece_scan), on the read's first words where it starts at position 0
     bool head = false;
@@ -904,28 +988,64 @@ ATR_DEV PieceScan piece_scan_spec(const uint32_t (&pl)[NW][4], const uint32_t (&
     for (int u = 0; u < PIECE_NT; ++u)
 #pragma unroll
         for (int w = 0; w < TWN; ++w) tocc[u][w] = spec::PP.tmask[u][w];
-    // Every term is a volatile one-instruction asm, in source order: left to itself the scheduler moves the ands of a
-    // step behind the in-place shift that follows them, keeps copies of every older mask and spills a hundred
-    // registers (round 5, first try).  In this order the live set is Y + occ + tocc = 52 registers.
-    const auto term = [](uint32_t &acc, uint32_t y, bool first) {
-        if (first) acc = y;                                          // (occ starts as all ones: the first term is a copy;
-        else asm volatile("v_and_b32 %0, %0, %1" : "+v"(acc) : "v"(y));   //  a read-end piece starts from its end mask)
+    // (every term is a volatile one-instruction asm, in source order: piece_asm_and.  Live: the masks + occ + tocc, 52
+    //  registers with four masks, 47 with two planes)
+    // c: the plane index of the term's code, a literal.  Two planes: one v_bitop3 on three distinct registers (table
+    // index = acc << 2 | H << 1 | L), or the and with Y0 for code 0.
+    const auto term = [&](uint32_t &acc, auto cc, int w, bool first) {
+        constexpr int c = decltype(cc)::value;
+        if constexpr (!TWO) {
+            if (first) acc = Y.y[c][w];                                  // (occ starts as all ones: the first term is a copy;
+            else piece_asm_and(acc, Y.y[c][w]);                          //  a read-end piece starts from its end mask)
+        } else if constexpr (c == 0) {
+            if (first) acc = Y0[w];
+            else piece_asm_and(acc, Y0[w]);
+        } else {
+            constexpr int TBL = c == 1 ? 0x20 : c == 2 ? 0x40 : 0x80;    // acc & ~H & L, acc & H & ~L, acc & H & L
+            if (first) acc = c == 1 ? (~H[w] & L[w]) : c == 2 ? (H[w] & ~L[w]) : (H[w] & L[w]);
+            else piece_asm_bitop3<TBL>(acc, H[w], L[w]);
+        }
+    };
+    // H, L and Y0 one position up, word w: the carry into word w + 1 waits behind that word's (independent) terms
+    uint64_t cyh = 0, cyl = 0, cy0 = 0;
+    const auto shift_word = [&](auto wc) {
+        constexpr int w = decltype(wc)::value;
+        piece_shift3<w == 0>(H[w], L[w], Y0[w], cyh, cyl, cy0);
     };
     piece_static_for<0, spec::PP.steps>([&](auto sc) {
         constexpr int s = decltype(sc)::value;
         constexpr uint32_t cw = spec::PP.scode[s];
+        if constexpr (TWO) {
+            // word by word: every term of the step on word w, then the shift of word w
+            piece_static_for<0, NW>([&](auto wc) {
+                constexpr int w = decltype(wc)::value;
+                piece_static_for<0, PIECE_NB>([&](auto pc) {
+                    constexpr int p = decltype(pc)::value;
+                    if constexpr (p < spec::PP.nb && s < spec::PP.plen[p]) term(occ[p][w], PieceIC<(int)((cw >> (2 * p)) & 3u)>{}, w, s == 0);
+                });
+                if constexpr (s < spec::PP.tlen && w >= TW0) {
+                    piece_static_for<0, PIECE_NT>([&](auto uc) {
+                        constexpr int u = decltype(uc)::value;
+                        // (a word in which the piece may not end stays zero: no term)
+                        if constexpr (spec::PP.tmask[u][w - TW0] != 0u)
+                            term(tocc[u][w - TW0], PieceIC<(int)((cw >> (PIECE_TBIT + 2 * u)) & 3u)>{}, w, false);
+                    });
+                }
+                if constexpr (s + 1 < spec::PP.steps) shift_word(wc);
+            });
+        } else {
         // (the regular pieces word by word, then the last piece: the order rounds 5's kernel was tuned in)
 #pragma unroll
         for (int w = 0; w < NW; ++w)
             piece_static_for<0, PIECE_NB>([&](auto pc) {
                 constexpr int p = decltype(pc)::value;
-                if constexpr (p < spec::PP.nb - 1 && s < spec::PP.plen[p]) term(occ[p][w], Y.y[(cw >> (2 * p)) & 3u][w], s == 0);
+                if constexpr (p < spec::PP.nb - 1 && s < spec::PP.plen[p]) term(occ[p][w], PieceIC<(int)((cw >> (2 * p)) & 3u)>{}, w, s == 0);
             });
         {
             constexpr int p = spec::PP.nb - 1;
             if constexpr (s < spec::PP.plen[p]) {
 #pragma unroll
-                for (int w = 0; w < NW; ++w) term(occ[p][w], Y.y[(cw >> (2 * p)) & 3u][w], s == 0);
+                for (int w = 0; w < NW; ++w) term(occ[p][w], PieceIC<(int)((cw >> (2 * p)) & 3u)>{}, w, s == 0);
             }
         }
         if constexpr (s < spec::PP.tlen) {
@@ -933,9 +1053,10 @@ ATR_DEV PieceScan piece_scan_spec(const uint32_t (&pl)[NW][4], const uint32_t (&
                 constexpr int u = decltype(uc)::value;
                 if constexpr ((spec::PP.tmask[u][0] | spec::PP.tmask[u][1] | spec::PP.tmask[u][2]) != 0u) {
 #pragma unroll
-                    for (int w = 0; w < TWN; ++w) term(tocc[u][w], Y.y[(cw >> (PIECE_TBIT + 2 * u)) & 3u][TW0 + w], false);
+                    for (int w = 0; w < TWN; ++w) term(tocc[u][w], PieceIC<(int)((cw >> (PIECE_TBIT + 2 * u)) & 3u)>{}, TW0 + w, false);
                 }
             });
+        }
         }
         if constexpr (spec::PP.sr != 0 && s < spec::PP.slen) {
             constexpr uint32_t cw2 = spec::PP.scode2[s];
@@ -943,12 +1064,14 @@ ATR_DEV PieceScan piece_scan_spec(const uint32_t (&pl)[NW][4], const uint32_t (&
                 constexpr int u = decltype(uc)::value;
                 if constexpr ((spec::PP.smask[u][0] | spec::PP.smask[u][1]) != 0u) {
 #pragma unroll
-                    for (int w = 0; w < HWN; ++w) term(socc[u][w], YH.y[(cw2 >> (2 * u)) & 3u][w], false);
+                    for (int w = 0; w < HWN; ++w) {
+                        piece_asm_and(socc[u][w], YH.y[(cw2 >> (2 * u)) & 3u][w]);
+                    }
                 }
             });
             if constexpr (s + 1 < spec::PP.slen) piece_shift_masks<HWN>(YH);
         }
-        if constexpr (s + 1 < spec::PP.steps) piece_shift_masks<NW>(Y);
+        if constexpr (!TWO && s + 1 < spec::PP.steps) piece_shift_masks<NW>(Y);
     });
     if constexpr (spec::PP.sr != 0 && spec::PP.slen > 0) {
         uint32_t any = 0u;
@@ -978,7 +1101,7 @@ ATR_DEV PieceScan piece_scan_spec(const uint32_t (&pl)[NW][4], const uint32_t (&
         for (int w = 0; w < NW; ++w) {
             const uint32_t lo = sh >= 32 ? (w + 1 < NW ? occ[p][w + 1 < NW ? w + 1 : w] : 0u) : occ[p][w];
             const uint32_t hi = sh >= 32 ? (w + 2 < NW ? occ[p][w + 2 < NW ? w + 2 : w] : 0u) : (w + 1 < NW ? occ[p][w + 1 < NW ? w + 1 : w] : 0u);
-            const uint32_t al = (sh & 31) ? __builtin_amdgcn_alignbit(hi, lo, (uint32_t)(sh & 31)) : lo;
+            const uint32_t al = (sh & 31) ? piece_funnel(hi, lo, sh & 31) : lo;
             dm[w] |= al;
             pf[w] &= al;
         }

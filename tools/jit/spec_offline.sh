@@ -10,7 +10,7 @@ OUT=${SPEC_OUT:-/tmp/w/spec}
 mkdir -p "$OUT" "$ROOT/build/csrc"
 CS=$ROOT/atropos_amd/csrc
 make -s -C "$CS" "$ROOT/build/csrc/jit_sources.inc" >/dev/null 2>&1 || (cd "$CS" && python3 embed_sources.py ../../build/csrc/jit_sources.inc piece_spec.hip tail_spec.hip piece_filter.hpp tail_filter.hpp fast_work.hpp pack_fast.hpp piece_core.hpp filter_core.hpp locate_core.hpp ../../include/atropos_hip.h)
-if [ ! -x "$OUT/spec_offline" ] || [ "$ROOT/tools/jit/spec_offline.cpp" -nt "$OUT/spec_offline" ] || [ "$CS/jit.hpp" -nt "$OUT/spec_offline" ] || [ "$CS/piece_core.hpp" -nt "$OUT/spec_offline" ]; then
+if [ ! -x "$OUT/spec_offline" ] || [ "$ROOT/tools/jit/spec_offline.cpp" -nt "$OUT/spec_offline" ] || [ "$CS/jit.hpp" -nt "$OUT/spec_offline" ] || [ "$CS/jit_config.hpp" -nt "$OUT/spec_offline" ] || [ "$CS/piece_core.hpp" -nt "$OUT/spec_offline" ]; then
   /opt/rocm/bin/hipcc -O1 -std=c++17 --offload-arch=gfx950 -x hip -I"$CS" -I"$ROOT/include" -I"$ROOT/build/csrc" "$ROOT/tools/jit/spec_offline.cpp" -o "$OUT/spec_offline" -ldl 2>&1 | grep -v warning || true
 fi
 "$OUT/spec_offline" "$AD" "$E" "$FL" "$MO" "$LEN" "$RG" "$OUT" $SPEC_RTC
