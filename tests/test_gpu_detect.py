@@ -1,8 +1,5 @@
 """GPU tier of known-contaminant detection: the reference's golden cases on the device, the device against the CPU
 twin on 1 M synthetic reads and against a plain-Python restatement on a slice of them, the file drivers."""
-import math
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -11,11 +8,11 @@ from atropos_amd import _lib, detect, synth
 from atropos_amd.fastq import FastqBatch
 
 from . import _detect_common as DC
+from ._detect_kernels_common import COMP, python_counters  # noqa: F401  (the model lives with the per-kernel checks)
 
 pytestmark = pytest.mark.gpu
 
 SLICE = 20000            # reads the plain-Python restatement looks at (about 15 s on one core)
-COMP = {a: b for a, b in zip("ACGTRYSWKMBDHVNacgtryswkmbdhvn", "TGCAYRSWMKVHDBNtgcayrswmkvhdbn")}
 
 
 @pytest.mark.parametrize("name", DC.case_names())
@@ -27,60 +24,6 @@ def test_golden_case_on_the_device(name, hip_backend):
 
 def synth_text(n, seed, known, length=150):
     return synth.contaminated_fastq(n, seed, known, length)
-
-
-def entropy_of_acgt(seq):
-    """The reference's complexity measure, written out here so that the restatement below stands alone."""
-    up = seq.upper()
-    h = 0
-    for b in ("A", "C", "G", "T"):
-        c = up.count(b)
-        if c > 0:
-            p = c / float(len(up))
-            h += p * math.log(p) / math.log(2)
-    return -h
-
-
-def python_counters(reads, items, kmer_size, past_end, frac):
-    """The contract restated in plain Python (not the twin): per known sequence (matches, hits, max_n, abundance)."""
-    regexp = re.compile("|".join(b + "{8,}.*|" + b + "{2,}$" for b in past_end))
-    min_k = min(len(s) for s, _ in items)
-    kept = set()
-    for seq in reads:
-        if entropy_of_acgt(seq) <= 1.0:
-            continue
-        m = regexp.search(seq)
-        if m:
-            seq = seq[:m.start()]
-        if len(seq) >= kmer_size and len(seq) >= min_k:
-            kept.add(seq)
-    post = {}
-    n_kmers = []
-    for s, (seq, _) in enumerate(items):
-        kmers = set(seq[i:i + kmer_size] for i in range(len(seq) - kmer_size + 1))
-        n_kmers.append(len(kmers))
-        for k in kmers:
-            post.setdefault(k, []).append(s)
-    out = np.zeros((4, len(items)), dtype=np.int64)
-    for seq in kept:
-        rc = "".join(COMP[c] for c in reversed(seq))
-        found = []
-        for strand in (seq, rc):
-            hit = {}
-            for k in set(strand[i:i + kmer_size] for i in range(len(strand) - kmer_size + 1)):
-                for s in post.get(k, ()):
-                    hit[s] = hit.get(s, 0) + 1
-            found.append(hit)
-        for s in set(found[0]) | set(found[1]):
-            n = max(found[0].get(s, 0), found[1].get(s, 0))
-            out[0, s] += n
-            if n / n_kmers[s] > frac:
-                out[1, s] += 1
-                out[2, s] = max(out[2, s], n)
-        for s, (known, _) in enumerate(items):
-            if known in seq:
-                out[3, s] += 1
-    return len(kept), out
 
 
 def _counters(det):
