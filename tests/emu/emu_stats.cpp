@@ -3,9 +3,10 @@
 // counted as stats_scalar_kernel and stats_position_kernel count it together; the counters are sums and maxima, so
 // the order does not matter.
 // NOTE: unlike the other twins this one RESTATES the per-read counting of stats_kernels.hip (the kernels have no
-// per-lane header to compile here); only the layout and the rounding are shared code.  A change to what the kernels
-// count is caught by the GPU test that compares this twin's blocks with the kernels' (tests/test_gpu_pairtext.py),
-// not by a CPU run.
+// per-lane header to compile here); only the layout and the rounding are shared code.  What pins it: the plain Python
+// model of tests/_stats_kernels_common.py (which shares neither), block for block -- tests/test_stats_kernels_host.py
+// compares this twin with it on the CPU, tests/test_gpu_stats_kernels.py the kernels, case for case the same.  A
+// change to what the kernels count fails the second; the same change made here fails the first.
 #include <limits.h>
 #include <stdint.h>
 #include <string.h>
