@@ -234,7 +234,14 @@ PROTOTYPES = {
     "atr_gzip_blocks": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [STREAM]),
     "atr_bgzf_scan": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4),
     "atr_gunzip_members": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 2 + [STREAM]),
+    "atr_gunzip_stream_workspace": (C.c_int64, [C.c_int64] * 3),
+    "atr_gunzip_stream": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64,
+                                    C.c_void_p, C.c_int64, C.c_void_p, STREAM]),
 }
+# atr_gunzip_stream: the words of d_result, the two statuses that ask for a larger slab / more room (the others: INF_E_*)
+GUNZIP_STREAM_WORDS = ("status", "end_bit", "text_len", "final_seen", "crc_out", "chunks", "confirmed", "redecoded")
+GUNZIP_NEED_INPUT, GUNZIP_NEED_ROOM = 101, 102
+GUNZIP_STREAM_MAX = (1 << 28) - 1        # bytes of one slab
 GZIP_BLOCK = 65280                       # atr_gzip_blocks: bytes of text per BGZF member
 GUNZIP_MAX_MEMBERS = 1 << 22             # atr_gunzip_members: members of one call (ATR_GUNZIP_MAX_MEMBERS)
 GZIP_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")  # atr_gzip_eof
@@ -988,7 +995,30 @@ class FastaCalls(object):
         return out[:total]
 
 
-class HipBackend(AbiCalls, PairTextCalls, StatsCalls, FastaCalls):
+class GunzipStreamCalls(object):
+    """The wrappers of the stream gunzip entry points (an ordinary .gz member inflated on the device), written against
+    ``_call`` / ``_host`` / ``empty`` like ``AbiCalls``' methods.  A mixin of its own: the CPU test-suite serves these
+    entry points from a twin library of their own (tests/emu/emu_gunzip_stream.cpp)."""
+
+    def gunzip_stream_workspace(self, n_stream, chunk_bytes, capacity):
+        return self._host("atr_gunzip_stream_workspace", int(n_stream), int(chunk_bytes), int(capacity))
+
+    def gunzip_stream(self, stream, n_stream, start_bit, window, window_len, crc_in, text, capacity, chunk_bytes, work=None):
+        """Inflate the blocks of ONE deflate stream that begin at bit ``start_bit`` of ``stream[:n_stream]`` (uint8 device
+        tensor) into ``text[:capacity]``; ``window[:window_len]``: the text before them, ``crc_in`` its CRC-32 so far;
+        ``chunk_bytes``: the spacing of the speculative starts.  Returns the 8 int64 result words on the device
+        (``GUNZIP_STREAM_WORDS``): nothing here waits for the kernels.  ``work``: a uint8 device tensor of at least
+        ``gunzip_stream_workspace`` bytes to use again."""
+        need = self.gunzip_stream_workspace(n_stream, chunk_bytes, capacity)
+        if work is None or work.numel() < need:
+            work = self.empty((need,), torch.uint8)
+        result = self.empty((len(GUNZIP_STREAM_WORDS),), torch.int64)
+        self._call("atr_gunzip_stream", _ptr(stream), int(n_stream), int(start_bit), _ptr(window), int(window_len),
+                   int(crc_in) & 0xffffffff, _ptr(text), int(capacity), int(chunk_bytes), _ptr(work), work.numel(), _ptr(result))
+        return result
+
+
+class HipBackend(AbiCalls, PairTextCalls, StatsCalls, FastaCalls, GunzipStreamCalls):
     """Thin object view of the C ABI; all buffers are torch tensors on one GPU.  The calls the CPU test-suite's stand-in
     serves as well are ``AbiCalls``'; here are the plumbing under them and the device-only calls."""
 

@@ -134,14 +134,17 @@ GZ_HD int inf_scan(const uint8_t *buf, int64_t n, int64_t max_members, int64_t *
 }
 
 // ---------------------------------------------------------------------------------------------- the member
-struct InfLds {
-    uint32_t out[INF_MAX_TEXT / 4];        // the member's text
+struct InfTables {                         // what the codes of a block take (shared with inflate_stream_core.hpp)
     uint32_t crc_tab[256];
     uint32_t lane_a[INF_NT];               // per lane: the CRC of its positions
     uint32_t cnt[16];                      // codes per length of the code being built
     uint16_t sym[3][INF_LL];               // symbols sorted by (length, symbol): literal/length, distance, code-length
     uint8_t seq[INF_LL + INF_D];           // the code lengths of a block: HLIT of them, then HDIST
     uint8_t cl_len[INF_CL + 1];
+};
+
+struct InfLds : InfTables {
+    uint32_t out[INF_MAX_TEXT / 4];        // the member's text
 };
 
 enum { INF_T_LL = 0, INF_T_D = 1, INF_T_CL = 2 };
@@ -155,7 +158,7 @@ struct InfWave {
 };
 
 struct InfCtx {
-    InfLds *L;
+    InfTables *L;            // (inf_member: an InfLds)
     const uint8_t *src;      // the member
     uint32_t msize;          // 26 .. INF_MAX_MEMBER
     uint8_t *dst;            // its text
@@ -207,7 +210,7 @@ ATR_DEV uint32_t inf_peek(const InfCtx &c, InfWave &W, uint32_t bitpos) {
 
 // The canonical code over lens[0 .. n): counts per length (a lane per length), the Kraft sum, every lane's lim / base,
 // the symbols in (length, symbol) order (a lane per length).  -> INF_B_*
-ATR_DEV int inf_build(InfLds *L, InfWave &W, int t, const uint8_t *lens, uint32_t n) {
+ATR_DEV int inf_build(InfTables *L, InfWave &W, int t, const uint8_t *lens, uint32_t n) {
     INF_SYNC();                                            // (lens[] written, the table before it read)
     INF_LANES(
         if (lane < 16) {
@@ -244,7 +247,7 @@ ATR_DEV int inf_build(InfLds *L, InfWave &W, int t, const uint8_t *lens, uint32_
 
 // the header of a dynamic block: the code-length code, then HLIT + HDIST code lengths into seq[]
 ATR_DEV int inf_dynamic(const InfCtx &c, InfWave &W, uint32_t &bitpos, uint32_t endbits, uint32_t &hlit, uint32_t &hdist) {
-    InfLds *L = c.L;
+    InfTables *L = c.L;
     const uint8_t order[INF_CL] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
     uint32_t v = inf_peek(c, W, bitpos);
     hlit = (v & 31u) + 257u;
@@ -291,7 +294,7 @@ ATR_DEV int inf_dynamic(const InfCtx &c, InfWave &W, uint32_t &bitpos, uint32_t 
 }
 
 // the codes of a fixed block as code lengths: 288 literal/length, then 32 distance
-ATR_DEV void inf_fixed(InfLds *L) {
+ATR_DEV void inf_fixed(InfTables *L) {
     INF_SYNC();
     INF_LANES(
         for (uint32_t i = (uint32_t)lane; i < INF_LL + INF_D; i += INF_NT)
@@ -301,7 +304,7 @@ ATR_DEV void inf_fixed(InfLds *L) {
 
 // the tokens of a coded block, up to its end-of-block
 ATR_DEV int inf_tokens(const InfCtx &c, InfWave &W, uint32_t &bitpos, uint32_t endbits, uint32_t &pos) {
-    InfLds *L = c.L;
+    InfLds *L = static_cast<InfLds *>(c.L);
     uint8_t *out = (uint8_t *)L->out;
     for (;;) {
         uint32_t v = inf_peek(c, W, bitpos);
@@ -351,7 +354,7 @@ ATR_DEV int inf_tokens(const InfCtx &c, InfWave &W, uint32_t &bitpos, uint32_t e
     }
 }
 
-ATR_DEV void inf_crc_table(InfLds *L) {
+ATR_DEV void inf_crc_table(InfTables *L) {
     INF_LANES(for (uint32_t i = (uint32_t)lane; i < 256; i += INF_NT) L->crc_tab[i] = gz_crc_entry(i))
     INF_SYNC();
 }
@@ -384,7 +387,7 @@ ATR_DEV uint32_t inf_crc(InfLds *L, uint32_t n) {
 // One member: header, blocks, ISIZE, CRC, and only then its text into dst[0 .. n_out).  L->crc_tab is filled.
 // Every lane of the wave calls it (device), or the emulation calls it once.  -> INF_OK or INF_E_*
 ATR_DEV int inf_member(const InfCtx &c) {
-    InfLds *L = c.L;
+    InfLds *L = static_cast<InfLds *>(c.L);
     InfWave W;
     W.cbase = 0xffffffffu;
     uint32_t data_at = 0, bsize = 0;

@@ -9,6 +9,7 @@ object exists anywhere on this path.
 """
 import collections
 import os
+import struct
 import time
 from concurrent.futures import ThreadPoolExecutor
 from contextlib import ExitStack
@@ -475,6 +476,14 @@ class StageClock(object):
         self.seconds[stage] = self.seconds.get(stage, 0.0) + (time.perf_counter() - t0)
 
 
+class _NotBgzf(Exception):
+    """(inside the reader) The BGZF walk met a member that is none, at this file offset."""
+
+    def __init__(self, offset):
+        Exception.__init__(self, offset)
+        self.offset = offset
+
+
 class ChunkedFastqReader(object):
     """Feeds a FASTQ file to the GPU in chunks of whole records.  The file is read straight into
     page-locked staging buffers (``IO_THREADS`` ``pread`` slices per chunk, no intermediate bytes objects).
@@ -501,6 +510,13 @@ class ChunkedFastqReader(object):
     ``inflate_path`` says which road a reader took: "device", "host" (any other ``.gz``: unchanged), or None.  The flag
     wants BGZF throughout: a later member that is not BGZF, or one that fails its checks, is a ``gzip.BadGzipFile``
     naming the member's file offset; a file that ends inside a member is an ``EOFError``.
+
+    ``device_gunzip="any"``: every other ``.gz`` member -- an ordinary gzip file, and an ordinary member behind BGZF ones,
+    which ``True`` refuses -- is inflated on the device as well (``gunzip_stream``: the deflate stream split
+    speculatively; ``inflate_path == "stream"``).  The host parses the member headers, issues one call per
+    slab of compressed bytes into the chunk's text tensor, reads the call's eight result words back (the next call
+    starts at their ``end_bit``), keeps the last 32 KiB of text as the next call's window and checks CRC-32 and ISIZE at
+    a member's end.  A chunk holds at least one deflate block.
 
     ``byte_range`` = (lo, hi): only these bytes of a plain file, which must be whole records (a rank's shard,
     ``shard.fastq_shard_ranges``).  The loop that drives a reader -- ``next_batch``, ``advance``, ``close``, and two
@@ -532,9 +548,15 @@ class ChunkedFastqReader(object):
         self.pos, self.size = byte_range or (0, os.path.getsize(path))      # (plain files: the next pread, the end)
         self.stream = None
         self.inflate_path = "host" if name.endswith(".gz") else None
+        self.any_gzip = device_gunzip == "any"
+        # (bgzf: the device road -- next_batch, advance, close; gz_stream: its chunks come from _assemble_stream)
         self.bgzf = bool(device_gunzip and name.endswith(".gz") and self._starts_with_bgzf())
+        self.gz_stream = bool(self.any_gzip and name.endswith(".gz") and not self.bgzf)
         if self.bgzf:
             self.inflate_path = "device"
+        elif self.gz_stream:
+            self.bgzf = True
+            self.inflate_path = "stream"
         elif name.endswith(".gz"):
             import gzip
             self.stream = gzip.open(self.file, "rb")
@@ -563,7 +585,9 @@ class ChunkedFastqReader(object):
             self.uploaded = [None] * len(self.buf)
             self.data = None
             try:
-                for _ in range(self.READ_AHEAD):
+                if self.gz_stream:
+                    self._stream_begin(0)
+                for _ in range(0 if self.gz_stream else self.READ_AHEAD):
                     self.reads.append(self.ahead.submit(self._read_slab))
                 self.pending = self._assemble_device(None)
             except BaseException:
@@ -679,7 +703,9 @@ class ChunkedFastqReader(object):
             text_at += [text_at[-1] + v for v in t_at[1:n + 1].tolist()]
             k += n
             covered += took
-            if not ok:
+            if not ok and self.any_gzip:
+                error = _NotBgzf(self.pos + covered)          # (device_gunzip="any": the stream road goes on from here)
+            elif not ok:
                 import gzip
                 error = gzip.BadGzipFile("not a BGZF member at file offset %d (device_gunzip wants BGZF throughout)" % (self.pos + covered))
             if not ok or n < self.BGZF_SCAN:
@@ -701,9 +727,18 @@ class ChunkedFastqReader(object):
 
     def _assemble_device(self, carry):
         """The next chunk: [carried-over text | the text of the next slab's members], both put there on the device."""
+        if self.gz_stream:
+            return self._assemble_stream(carry)
         t0 = time.perf_counter()
         slot, pos, n, member_at, text_at, final, error = self.reads.popleft().result()
         self.clock.add("wait_file_read", t0)
+        if isinstance(error, _NotBgzf):                       # an ordinary member behind BGZF members
+            for fut in self.reads:
+                fut.exception()
+            self.reads.clear()
+            self.gz_stream = True
+            self._stream_begin(error.offset)
+            return self._assemble_stream(carry)
         if error is not None:
             return error                                      # (raised when this chunk is asked for)
         k, total = len(member_at) - 1, text_at[-1]
@@ -758,6 +793,190 @@ class ChunkedFastqReader(object):
                 self.upload_stream.wait_stream(torch.cuda.current_stream(self.be.device))
         self.data, self.nbytes = data, nbytes
         return data, nbytes, unterminated
+
+    # ---- any other .gz input (device_gunzip="any"): member by member, slab by slab, inflated speculatively on the device
+    # compressed bytes per speculative start (atr_gunzip_stream): the one serial wave resolves 32 KiB of text per
+    # confirmed chunk, so a chunk should hold many times that; 128 KiB is some 300 - 600 KB of FASTQ
+    STREAM_SPACING = 131072
+
+    def _stream_begin(self, offset):
+        """The stream road from file offset ``offset`` on, where a member's header stands (or the file ends)."""
+        self.z_pos = offset                                   # file offset of slab byte 0
+        self.z_n = 0                                          # bytes of the slab (self.buf[0])
+        self.z_at = 0                                         # next byte of the slab: a header, or (in a member) unused
+        self.z_dev = None                                     # the slab on the device
+        self.z_member = None                                  # file offset of the member being inflated
+        self.z_bit = 0                                        # ... and the bit of the slab its next block starts at
+        self.z_crc = self.z_isize = 0
+        self.z_window = self.be.empty((32768,), torch.uint8)
+        self.z_wlen = 0
+        self.z_work = None
+        self.z_done = False
+        self.z_spacing = min(self.STREAM_SPACING, max(256, self.chunk_bytes // 64))
+
+    def _stream_load(self, start, want):
+        """Slab := the file's bytes [start, start + want), as far as the file goes."""
+        want = max(0, min(want, self.buf[0].numel() - 32, _lib.GUNZIP_STREAM_MAX, self.size - start))
+        view = memoryview(self.buf[0].numpy())
+        step = ((want + IO_THREADS - 1) // IO_THREADS + 4095) & ~4095
+        jobs = []
+        for t in range(IO_THREADS):
+            lo, hi = t * step, min(want, (t + 1) * step)
+            if hi > lo:
+                jobs.append(self.readers.submit(os.preadv, self.fd, [view[lo:hi]], start + lo))
+        if sum(j.result() for j in jobs) != want:
+            raise IOError("short read: the input file changed while it was being read")
+        self.z_bit -= 8 * (start - self.z_pos)
+        self.z_at -= start - self.z_pos
+        self.z_pos, self.z_n, self.z_dev = start, want, None
+
+    def _stream_more(self, keep_from, budget):
+        """A slab that begins at slab byte ``keep_from`` and is larger than what is left behind it; -> False at the file's end."""
+        if self.z_pos + self.z_n >= self.size:
+            return False
+        left = self.z_n - keep_from
+        self._stream_load(self.z_pos + keep_from, max(2 * left, int(budget * self.ratio * 1.25) + (128 << 10)))
+        if self.z_n <= left:
+            raise ValueError("a deflate block or a gzip header of more than %d bytes at file offset %d" % (left, self.z_pos))
+        return True
+
+    def _stream_header(self, buf, at, end, at_eof):
+        """The gzip member header at slab byte ``at``: -> the byte its deflate data starts at, or None: not all there.
+        What Python's gzip module refuses is refused with its exception."""
+        import gzip
+
+        def short():
+            if at_eof:
+                raise EOFError("Compressed file ended before the end-of-stream marker was reached")
+
+        if end - at < 2:
+            if at_eof:
+                raise gzip.BadGzipFile("Not a gzipped file (%r)" % bytes(buf[at:end]))
+            return None
+        if buf[at] != 0x1f or buf[at + 1] != 0x8b:
+            raise gzip.BadGzipFile("Not a gzipped file (%r) at file offset %d " % (bytes(buf[at:at + 2]), self.z_pos + at))
+        if end - at < 10:
+            return short()
+        if buf[at + 2] != 8:
+            raise gzip.BadGzipFile("Unknown compression method at file offset %d " % (self.z_pos + at))
+        flags, p = int(buf[at + 3]), at + 10
+        if flags & 4:                                         # FEXTRA
+            if end - p < 2:
+                return short()
+            p += 2 + int(buf[p]) + 256 * int(buf[p + 1])
+        for bit in (8, 16):                                   # FNAME, FCOMMENT: zero-terminated
+            if flags & bit:
+                while p < end and buf[p]:
+                    p += 1
+                p += 1
+        if flags & 2:                                         # FHCRC
+            p += 2
+        return p if p <= end else short()
+
+    def _assemble_stream(self, carry):
+        """The next chunk: [carried-over text | text of the members' blocks, as much as the chunk takes]."""
+        try:
+            return self._assemble_stream_or_raise(carry)
+        except Exception as e:                                # noqa: BLE001 (raised when this chunk is asked for)
+            return e
+
+    def _assemble_stream_or_raise(self, carry):
+        import gzip
+        import zlib
+        be = self.be
+        n0 = carry[2] - carry[1] if carry else 0
+        budget = max(self.chunk_bytes - n0, self.chunk_bytes // 4)
+        data = be.empty(((n0 + budget + 15) // 16 * 16 + 32,), torch.uint8)
+        if n0:
+            data[:n0].copy_(carry[0][carry[1]:carry[2]])
+        filled = 0
+        buf = self.buf[0].numpy()
+        while not self.z_done and filled < budget:
+            t0 = time.perf_counter()
+            at_eof = self.z_pos + self.z_n >= self.size
+            if self.z_member is None:                         # between members: zero padding, the end, or a header
+                while self.z_at < self.z_n and buf[self.z_at] == 0 and self.z_pos + self.z_at > 0:
+                    self.z_at += 1
+                if self.z_at >= self.z_n:
+                    if at_eof:
+                        self.z_done = True
+                        break
+                    self._stream_load(self.z_pos + self.z_at, int(budget * self.ratio * 1.25) + (128 << 10))
+                    self.clock.add("wait_file_read", t0)
+                    continue
+                start = self._stream_header(buf, self.z_at, self.z_n, at_eof)
+                if start is None:
+                    self._stream_more(self.z_at, budget)
+                    self.clock.add("wait_file_read", t0)
+                    continue
+                self.z_member, self.z_bit = self.z_pos + self.z_at, 8 * start
+                self.z_crc = self.z_isize = self.z_wlen = 0
+            if self.z_dev is None:
+                n = self.z_n
+                self.z_dev = be.empty(((n + 15) // 16 * 16 + 16,), torch.uint8)
+                self.z_dev[:n].copy_(self.buf[0][:n], non_blocking=True)
+                self.z_dev[n:].zero_()
+            self.clock.add("wait_file_read", t0)
+            byte = self.z_bit // 8
+            room = budget - filled
+            need = be.gunzip_stream_workspace(self.z_n - byte, self.z_spacing, room)
+            if self.z_work is None or self.z_work.numel() < need:
+                self.z_work = be.empty((need,), torch.uint8)
+            res = be.gunzip_stream(self.z_dev[byte:], self.z_n - byte, self.z_bit - 8 * byte, self.z_window, self.z_wlen, self.z_crc,
+                                   data[n0 + filled:], room, self.z_spacing, work=self.z_work)
+            status, end_bit, got, final, crc = res.cpu().tolist()[:5]   # (the next call's first bit: the one wait of a call)
+            if status == _lib.GUNZIP_NEED_INPUT:
+                if not self._stream_more(byte, budget):
+                    raise EOFError("Compressed file ended before the end-of-stream marker was reached")
+                continue
+            if status == _lib.GUNZIP_NEED_ROOM:
+                if filled:
+                    break                                     # (the next chunk has all its room for this block)
+                budget *= 2                                   # a block of more text than a chunk: this chunk grows
+                grown = be.empty(((n0 + budget + 15) // 16 * 16 + 32,), torch.uint8)
+                grown[:n0].copy_(data[:n0])
+                data = grown
+                continue
+            if status:                                        # (what the host road's decompressor raises for bad deflate data)
+                raise zlib.error("Error -3 while decompressing data: the gzip member at file offset %d breaks rule %d of "
+                                 "inflate_core.hpp" % (self.z_member, status))
+            if got:
+                lo = n0 + filled
+                if got >= 32768:
+                    self.z_window.copy_(data[lo + got - 32768:lo + got])
+                    self.z_wlen = 32768
+                else:
+                    both = torch.cat([self.z_window[:self.z_wlen], data[lo:lo + got]])[-32768:]
+                    self.z_wlen = both.numel()
+                    self.z_window[:self.z_wlen].copy_(both)
+                self.ratio = max(end_bit / 8.0 / got, 0.001)
+            filled += got
+            self.z_crc, self.z_isize = crc, (self.z_isize + got) & 0xffffffff
+            self.z_bit = 8 * byte + end_bit
+            if not final:
+                # the slab ended inside a block, or the next block's text does not fit: the next call says which, at
+                # the price of decoding the rest of the slab once more -- so a chunk that is half full ends here
+                if got < room and 2 * filled >= budget:
+                    break
+                if got < room and self.z_pos + self.z_n < self.size:
+                    self._stream_more(self.z_bit // 8, budget)
+                continue
+            trailer = (self.z_bit + 7) // 8
+            if trailer + 8 > self.z_n:
+                if not self._stream_more(self.z_bit // 8, budget):
+                    raise EOFError("Compressed file ended before the end-of-stream marker was reached")
+                trailer = (self.z_bit + 7) // 8
+                if trailer + 8 > self.z_n:
+                    raise EOFError("Compressed file ended before the end-of-stream marker was reached")
+            want_crc, want_size = struct.unpack("<II", bytes(buf[trailer:trailer + 8]))
+            if want_crc != self.z_crc:
+                raise gzip.BadGzipFile("CRC check failed for the gzip member at file offset %d (%#x != %#x)" % (self.z_member, want_crc, self.z_crc))
+            if want_size != self.z_isize:
+                raise gzip.BadGzipFile("Incorrect length of data produced by the gzip member at file offset %d " % self.z_member)
+            self.z_member, self.z_at = None, trailer + 8
+        nbytes = n0 + filled
+        data[nbytes:nbytes + 32].zero_()
+        return nbytes, self.z_done, data[:(nbytes + 15) // 16 * 16 + 16], None, None, None, 0, None
 
     # ---- compressed input: one sequential decompressor, one chunk ahead
     def _fill(self, k, carry):
@@ -882,7 +1101,7 @@ def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, 
     The next chunk is put together, and its upload started, BEFORE a chunk is handed out: that copy runs while the
     consumer works.  A chunk may hold no whole record; it is yielded all the same.  The readers are closed when the
     loop ends, however it ends -- a consumer that has enough just leaves its ``for`` loop.  ``byte_ranges``: one
-    (lo, hi) or None per path (``ChunkedFastqReader``).  ``device_gunzip``: BGZF ``.gz`` input is inflated on the GPU
+    (lo, hi) or None per path (``ChunkedFastqReader``).  ``device_gunzip``: BGZF ``.gz`` input (``True``), or any ``.gz`` input (``"any"``), is inflated on the GPU
     (``ChunkedFastqReader``); every other input is read as without it.
 
     ``interleaved``: the one path holds pairs, read 1 and read 2 in turn (the reference's ``-l``): every list holds TWO

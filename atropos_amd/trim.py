@@ -950,8 +950,9 @@ class TrimPipeline(object):
 
         ``device_gunzip``: a ``path_in`` that ends in ``.gz`` and holds BGZF members (``bgzip``, htslib,
         ``device_gzip=True``) is inflated on the GPU, a wave per member, instead of by one host thread; any other
-        input is read as without the flag (``fastq.ChunkedFastqReader``).  It only changes where the text comes
-        from, and combines with every other option.
+        input is read as without the flag (``fastq.ChunkedFastqReader``).  ``device_gunzip="any"``: every other
+        ``.gz`` member -- an ordinary gzip file -- is inflated on the GPU as well (a speculative two-pass gunzip).
+        The flag only changes where the text comes from, and combines with every other option.
 
         FASTA: the input is read as FASTA when ``input_format`` = "fasta", else when its name ends in .fasta / .fa /
         .fna (a compression suffix aside), else when its first byte is '>' (``fastq.input_format``).  The output is

@@ -945,6 +945,31 @@ int atr_bgzf_scan(const uint8_t *buf, int64_t n_bytes, int64_t max_members, int6
 int atr_gunzip_members(const uint8_t *d_stream, int64_t n_stream, const int64_t *d_member_at, const int64_t *d_text_at,
                        int64_t n_members, uint8_t *d_text, int64_t text_capacity, int32_t *d_status, int32_t *d_bad, void *stream);
 
+/* ---- an ordinary .gz member inflated on the device (gunzip_stream_kernels.hip, inflate_stream_core.hpp) ---------------
+ * A deflate stream without a member table, split speculatively: block starts are guessed per chunk of chunk_bytes,
+ * every chunk is decoded with an unknown window, and only what a chain of confirmed block boundaries reaches is kept.
+ *   atr_gunzip_stream_workspace   bytes of d_workspace for a call with these sizes (ATR_ERR_INVALID: no such call)
+ *   atr_gunzip_stream   d_stream[0 .. n_stream) is a slab of ONE member's deflate data (n_stream < 2^28); a block starts at
+ *                       bit start_bit (any bit, <= 8 n_stream); d_window[0 .. window_len) is the text before it (at most
+ *                       32 768 bytes; 0 at a member's start) and crc_in the CRC-32 of the member's text so far.  The
+ *                       text of the blocks in [start_bit, end_bit) is written to d_text[0 .. text_len), exactly what zlib
+ *                       gives; end_bit is a block boundary: the bit behind the final block (final_seen), else the last
+ *                       boundary up to which the text fits text_capacity (< 2^31) and the blocks end inside the slab.  A
+ *                       caller goes on from end_bit with the last 32 KiB of text as the window and crc_out as crc_in.
+ *                       chunk_bytes (64 .. 2^24) is the spacing of the speculative starts.
+ *                       d_result: 8 int64 DEVICE words -- status, end_bit, text_len, final_seen, crc_out, chunks,
+ *                       confirmed (chunks whose start the chain reached, chunk 0 among them), redecoded (stretches
+ *                       decoded again from confirmed state).  status: 0; ATR_GUNZIP_NEED_INPUT / ATR_GUNZIP_NEED_ROOM
+ *                       when not one block ends inside the slab / fits the capacity (end_bit = start_bit); or the rule
+ *                       that corrupt data breaks (inflate_core.hpp INF_E_*), the text then being unspecified.
+ * Every store lies in d_text[0 .. text_capacity), the workspace or d_result.  Nothing here waits for the kernels. */
+#define ATR_GUNZIP_NEED_INPUT 101
+#define ATR_GUNZIP_NEED_ROOM 102
+int64_t atr_gunzip_stream_workspace(int64_t n_stream, int64_t chunk_bytes, int64_t text_capacity);
+int atr_gunzip_stream(const uint8_t *d_stream, int64_t n_stream, int64_t start_bit, const uint8_t *d_window, int32_t window_len,
+                      uint32_t crc_in, uint8_t *d_text, int64_t text_capacity, int64_t chunk_bytes, void *d_workspace,
+                      int64_t workspace_bytes, int64_t *d_result, void *stream);
+
 /* ---- device-resident FASTA batch -------------------------------------------------------------
  * The reference's FastaReader (io/seqio.py:233-280) over a chunk of text in device memory, under the
  * conditions of atr_fastq_index: below 4 GiB, 16-byte aligned, readable up to the next multiple of 16

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""The .gz input path on one MI355X.  The input is the BGZF file that ``trim_file(..., device_gzip=True)`` writes from
-tools/bench_fastq.py's generator (a pass-through pipeline: the file holds the generator's text).
+"""The .gz input path on one MI355X.  Two inputs hold the text of tools/bench_fastq.py's generator: the BGZF file that
+``trim_file(..., device_gzip=True)`` writes (a pass-through pipeline), and an ordinary gzip file: ONE member written by
+zlib at level 6, what a sequencer or an archive hands out.
 
-  (a) kernel : HipBackend.gunzip_members on the resident compressed chunk, GB/s of plain text
-  (b) file   : TrimPipeline.trim_file from that .gz into a plain file with device_gunzip=True, the same run with
-               device_gunzip=False (one host thread of zlib: the path before the flag, over fewer reads), and the run
-               from the plain file (the ceiling).  The three variants alternate, run after run.
+  (a) kernel : HipBackend.gunzip_members on the resident BGZF file ("kernel"), and HipBackend.gunzip_stream -- the
+               speculative inflater of device_gunzip="any" -- on the resident deflate data of the ordinary member
+               ("stream_kernel", with its chunks / confirmed / redecoded counts), GB/s of plain text
+  (b) file   : TrimPipeline.trim_file into a plain file from the BGZF file with device_gunzip=True, from the ordinary
+               file with device_gunzip="any", the same two runs with device_gunzip=False (one host thread of zlib: the
+               path before the flags, over fewer reads), and the run from the plain file (the ceiling).  The variants
+               alternate, run after run.
 
 Per timed variant: warm-up runs, then `runs` runs; the median and the spread (min .. max).  One JSON line.
 usage: tools/bench_gunzip.py [nreads] [runs] [warmup] [host_reads]   (host_reads: reads of the device_gunzip=False run)"""
@@ -15,6 +19,7 @@ import statistics
 import sys
 import tempfile
 import time
+import zlib
 
 import torch
 
@@ -81,8 +86,40 @@ def main():
         assert int(bad.item()) == 0 and bool((text[:nbytes] == data[:nbytes]).all()), "the inflated text is not the input"
         kernel = dict(text_bytes=nbytes, compressed_bytes=n, members=len(member_at) - 1, ms=spread(ms),
                       gb_per_s=nbytes / (statistics.median(ms) * 1e-3) / 1e9)
+        # the ordinary gzip files: one zlib level 6 member each
+        ordinary, small_ordinary = os.path.join(tmp, "ordinary.fastq.gz"), os.path.join(tmp, "small_ordinary.fastq.gz")
+        for text_bytes, dst in ((host, ordinary), (host[:host_reads * width], small_ordinary)):
+            co = zlib.compressobj(6, zlib.DEFLATED, 31)
+            with open(dst, "wb") as fh:
+                fh.write(co.compress(text_bytes) + co.flush())
+        # (a) the stream entry point alone: the member's deflate data resident (behind the 10-byte header), one call
+        raw = open(ordinary, "rb").read()
+        n = len(raw) - 10 - 8
+        assert n <= _lib.GUNZIP_STREAM_MAX and nbytes < (1 << 31) - 64, "fewer reads: one call takes a slab below 256 MiB"
+        buf = torch.zeros(((n + 15) // 16 * 16 + 16,), dtype=torch.uint8)
+        buf[:n] = torch.frombuffer(bytearray(raw[10:10 + n]), dtype=torch.uint8)
+        stream = buf.to(be.device)
+        window = be.empty((16,), torch.uint8)
+        spacing = 131072                                   # (ChunkedFastqReader.STREAM_SPACING)
+        work = be.empty((be.gunzip_stream_workspace(n, spacing, nbytes + 64),), torch.uint8)
+        text.zero_()
+        ms = []
+        for k in range(warmup + runs):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = be.gunzip_stream(stream, n, 0, window, 0, 0, text, nbytes + 16, spacing, work=work)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms.append((time.perf_counter() - t0) * 1e3)
+        words = dict(zip(_lib.GUNZIP_STREAM_WORDS, res.cpu().tolist()))
+        assert words["status"] == 0 and words["final_seen"] == 1 and words["text_len"] == nbytes and words["crc_out"] == zlib.crc32(host)
+        assert bool((text[:nbytes] == data[:nbytes]).all()), "the inflated text is not the input"
+        stream_kernel = dict(text_bytes=nbytes, compressed_bytes=n, spacing=spacing, chunks=words["chunks"], confirmed=words["confirmed"],
+                             redecoded=words["redecoded"], ms=spread(ms), gb_per_s=nbytes / (statistics.median(ms) * 1e-3) / 1e9)
+        del work
         # (b) file to file, the variants in turn
-        variants = (("plain", plain, nreads, False), ("device_gunzip", gz, nreads, True), ("host_gunzip", small_gz, host_reads, False))
+        variants = (("plain", plain, nreads, False), ("device_gunzip", gz, nreads, True), ("host_gunzip", small_gz, host_reads, False),
+                    ("any_gunzip", ordinary, nreads, "any"), ("host_gunzip_ordinary", small_ordinary, host_reads, False))
         secs = {name: [] for name, _, _, _ in variants}
         for k in range(warmup + runs):
             for name, path_in, reads, flag in variants:
@@ -93,11 +130,12 @@ def main():
                 torch.cuda.synchronize()
                 if k >= warmup:
                     secs[name].append(time.perf_counter() - t0)
-        outs = {name: open(os.path.join(tmp, name + ".out"), "rb").read() for name in ("plain", "device_gunzip")}
+        outs = {name: open(os.path.join(tmp, name + ".out"), "rb").read() for name in ("plain", "device_gunzip", "any_gunzip")}
         assert outs["plain"] == outs["device_gunzip"], "device_gunzip changes the output"
+        assert outs["plain"] == outs["any_gunzip"], "device_gunzip='any' changes the output"
         rates = {name: dict(reads=reads, seconds=spread(secs[name]), mreads_per_s=reads / statistics.median(secs[name]) / 1e6)
                  for name, _, reads, _ in variants}
-    print(json.dumps(dict(kernel=kernel, file_to_file=rates, runs=runs, warmup=warmup)), flush=True)
+    print(json.dumps(dict(kernel=kernel, stream_kernel=stream_kernel, file_to_file=rates, runs=runs, warmup=warmup)), flush=True)
 
 
 if __name__ == "__main__":
