@@ -237,6 +237,12 @@ PROTOTYPES = {
     "atr_gunzip_stream_workspace": (C.c_int64, [C.c_int64] * 3),
     "atr_gunzip_stream": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64,
                                     C.c_void_p, C.c_int64, C.c_void_p, STREAM]),
+    "atr_bam_header": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "atr_bam_walk_workspace": (C.c_int64, [C.c_int64] * 2),
+    "atr_bam_walk": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                               C.c_void_p, C.c_void_p, C.c_int64, STREAM]),
+    "atr_bam_to_fastq_work_bytes": (C.c_size_t, [C.c_int64]),
+    "atr_bam_to_fastq": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4 + [STREAM]),
 }
 # atr_gunzip_stream: the words of d_result, the two statuses that ask for a larger slab / more room (the others: INF_E_*)
 GUNZIP_STREAM_WORDS = ("status", "end_bit", "text_len", "final_seen", "crc_out", "chunks", "confirmed", "redecoded")
@@ -257,6 +263,14 @@ REPORT_VARIANTS = {"auto": 0, "lds": 1, "global": 2}
 
 FASTQ_ERR_AT, FASTQ_ERR_PLUS, FASTQ_ERR_NAME2, FASTQ_ERR_LENGTH = 1, 2, 3, 4
 FASTA_ERR_HEADER = 1
+# atr_bam_*: the result words of the walk and of the decode, their error kinds, the statuses, the product's sizes
+BAM_WALK_WORDS = ("count", "consumed", "error", "repaired")
+BAM_DECODE_WORDS = ("text_bytes", "error", "records")
+BAM_NEED_MORE = 1
+BAM_ERR_SMALL, BAM_ERR_BIG, BAM_ERR_LSEQ, BAM_ERR_TRUNCATED = 1, 2, 3, 4
+BAM_REC_LSEQ0, BAM_REC_QUAL, BAM_REC_NAME, BAM_REC_PAIR_NAME, BAM_REC_PAIR_FLAGS = 1, 2, 3, 4, 5
+BAM_TILE = 8192                          # atr_bam_walk: bytes per speculative tile (some 30 records of 150 bases)
+BAM_MAX_BLOCK = 64 << 20                 # the largest block_size: a record must fit a reader's carry (ChunkedFastqReader.RESERVE)
 DEST_KEEP, DEST_TOO_SHORT, DEST_TOO_LONG, DEST_TOO_MANY_N, DEST_TRIMMED, DEST_UNTRIMMED = range(6)
 INT64_MAX = (1 << 63) - 1
 EMIT_MAX_GROUPS = 1024                   # atr_fastq_emit_grouped: outputs per call
@@ -1018,7 +1032,54 @@ class GunzipStreamCalls(object):
         return result
 
 
-class HipBackend(AbiCalls, PairTextCalls, StatsCalls, FastaCalls, GunzipStreamCalls):
+class BamCalls(object):
+    """The wrappers of the unaligned BAM entry points (header, record walk, decode to FASTQ text), written against
+    ``_call`` / ``_host`` / ``empty`` like ``AbiCalls``' methods.  A mixin of its own: the CPU test-suite serves these
+    entry points from a twin library of their own (tests/emu/emu_bam.cpp)."""
+
+    def bam_header(self, buf):
+        """``buf``: bytes from the front of an inflated BAM stream.  (header bytes, n_ref), or None when ``buf`` ends
+        inside the header; another magic is a ValueError."""
+        raw = bytes(buf)
+        length, n_ref = C.c_int64(0), C.c_int32(0)
+        rc = self._host("atr_bam_header", C.c_char_p(raw), len(raw), C.byref(length), C.byref(n_ref))
+        return None if rc == BAM_NEED_MORE else (int(length.value), int(n_ref.value))
+
+    def bam_walk(self, data, nbytes, entry, n_ref, final, tile_bytes=BAM_TILE, max_block=BAM_MAX_BLOCK, work=None):
+        """The record starts of ``data[:nbytes]`` (uint8 device tensor, 16-byte aligned, padded to the next multiple of
+        16) from ``entry`` on.  Returns (starts int32 [capacity], the 4 int64 result words on the device:
+        ``BAM_WALK_WORDS``): nothing here waits for the kernels."""
+        need = self._host("atr_bam_walk_workspace", int(nbytes), int(tile_bytes))
+        if work is None or work.numel() < need:
+            work = self.empty((max(need, 16),), torch.uint8)
+        capacity = (int(nbytes) - int(entry)) // 36 + 1
+        starts = self.empty((capacity,), torch.int32)
+        result = self.empty((len(BAM_WALK_WORDS),), torch.int64)
+        self._call("atr_bam_walk", _ptr(data), int(nbytes), int(entry), int(n_ref), int(bool(final)), int(tile_bytes),
+                   int(max_block), _ptr(starts), capacity, _ptr(result), _ptr(work), work.numel())
+        return starts, result
+
+    def bam_to_fastq(self, data, nbytes, starts, n, paired=False):
+        """FASTQ text (uint8 device tensor, zero-padded to the next multiple of 16 and 16 bytes more) of the records
+        ``starts[:n]``; (text, its bytes, records written, error word, offsets int64 [written + 1])."""
+        n = int(n)
+        offsets = self.empty((n + 1,), torch.int64)
+        result = self.empty((len(BAM_DECODE_WORDS),), torch.int64)
+        work = self.empty((max(self._host("atr_bam_to_fastq_work_bytes", n), 16),), torch.uint8)
+        args = (_ptr(data), int(nbytes), _ptr(starts), n, int(bool(paired)), _ptr(offsets), _ptr(result), _ptr(work))
+        self._call("atr_bam_to_fastq", *args, None)
+        total, err, used = (int(v) for v in result.cpu().tolist())
+        if total >= (1 << 32) - 32:
+            raise ValueError("the FASTQ text of a BAM chunk must stay below 4 GiB; read the file in smaller chunks")
+        text = self.empty(((total + 15) // 16 * 16 + 16,), torch.uint8)
+        text[total:].zero_()
+        if used and err == INT64_MAX:
+            self._call("atr_bam_to_fastq", *args, _ptr(text))
+            err = int(result[1].item())
+        return text, total, used, err, offsets[:used + 1]
+
+
+class HipBackend(AbiCalls, PairTextCalls, StatsCalls, FastaCalls, GunzipStreamCalls, BamCalls):
     """Thin object view of the C ABI; all buffers are torch tensors on one GPU.  The calls the CPU test-suite's stand-in
     serves as well are ``AbiCalls``'; here are the plumbing under them and the device-only calls."""
 

@@ -17,6 +17,7 @@
 
 #include "atropos_hip.h"
 #include "fasta_core.hpp"
+#include "scan_kernels.hpp"
 
 namespace atr {
 
@@ -24,9 +25,6 @@ int hip_fail(hipError_t e, const char *what);             // api.hip
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int FA_SCAN = 1024;                             // threads (and elements) per block of the prefix sums
 constexpr int FA_NL = 256, FA_NL_BYTES = FA_NL * 16;      // line index: threads per block, bytes per block
 
 inline size_t fa_align(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -34,79 +32,6 @@ inline long long fa_blocks(long long n, long long per) { return (n + per - 1) / 
 inline int fa_launched(const char *what) {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ATR_OK : hip_fail(e, what);
-}
-
-// inclusive prefix sum of one value per thread over a block of THREADS; *total = the block's sum
-template <int THREADS>
-__device__ __forceinline__ u64 fa_block_scan(u64 v, u64 *s_part, u64 *total) {
-    constexpr int WAVES = THREADS / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u64 y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) s_part[wave] = x;
-    __syncthreads();
-    if (wave == 0) {
-        u64 w = lane < WAVES ? s_part[lane] : 0ull;
-#pragma unroll
-        for (int off = 1; off < WAVES; off <<= 1) {
-            const u64 y = __shfl_up(w, off, 64);
-            if (lane >= off) w += y;
-        }
-        if (lane < WAVES) s_part[lane] = w;
-    }
-    __syncthreads();
-    *total = s_part[WAVES - 1];
-    return x + (wave ? s_part[wave - 1] : 0ull);
-}
-
-// out[i] = exclusive prefix of v inside its block, sums[b] = the block's total
-__global__ __launch_bounds__(FA_SCAN) void fa_scan_local_kernel(const u64 *__restrict__ v, long long n, u64 *__restrict__ out,
-                                                                u64 *__restrict__ sums) {
-    __shared__ u64 s_part[FA_SCAN / 64];
-    const long long i = (long long)blockIdx.x * FA_SCAN + threadIdx.x;
-    const u64 x = i < n ? v[i] : 0ull;
-    u64 total;
-    const u64 inc = fa_block_scan<FA_SCAN>(x, s_part, &total);
-    if (i < n) out[i] = inc - x;
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// exclusive prefix of the nb block totals in place (one block, a run per thread); out[n] = the grand total
-__global__ __launch_bounds__(FA_SCAN) void fa_scan_sums_kernel(u64 *__restrict__ sums, long long nb, u64 *__restrict__ out,
-                                                               long long n) {
-    __shared__ u64 s_part[FA_SCAN / 64];
-    const long long per = (nb + FA_SCAN - 1) / FA_SCAN;
-    const long long lo = min(nb, per * (long long)threadIdx.x), hi = min(nb, lo + per);
-    u64 mine = 0;
-    for (long long i = lo; i < hi; ++i) mine += sums[i];
-    u64 total;
-    const u64 inc = fa_block_scan<FA_SCAN>(mine, s_part, &total);
-    u64 run = inc - mine;
-    for (long long i = lo; i < hi; ++i) { const u64 t = sums[i]; sums[i] = run; run += t; }
-    if (threadIdx.x == 0) out[n] = total;
-}
-
-__global__ __launch_bounds__(FA_SCAN) void fa_scan_add_kernel(u64 *__restrict__ out, long long n, const u64 *__restrict__ sums) {
-    const long long i = (long long)blockIdx.x * FA_SCAN + threadIdx.x;
-    if (i < n) out[i] += sums[blockIdx.x];
-}
-
-__global__ void fa_set_kernel(long long *p, long long v) { *p = v; }
-
-// out[0 .. n] = exclusive prefix sums of v[0 .. n), out[n] the total; sums: fa_blocks(n, FA_SCAN) words
-void fa_scan(const u64 *v, long long n, u64 *out, u64 *sums, hipStream_t st) {
-    if (n == 0) {
-        hipLaunchKernelGGL(fa_set_kernel, dim3(1), dim3(1), 0, st, (long long *)out, 0ll);
-        return;
-    }
-    const long long nb = fa_blocks(n, FA_SCAN);
-    hipLaunchKernelGGL(fa_scan_local_kernel, dim3((unsigned)nb), dim3(FA_SCAN), 0, st, v, n, out, sums);
-    hipLaunchKernelGGL(fa_scan_sums_kernel, dim3(1), dim3(FA_SCAN), 0, st, sums, nb, out, n);
-    hipLaunchKernelGGL(fa_scan_add_kernel, dim3((unsigned)nb), dim3(FA_SCAN), 0, st, out, n, (const u64 *)sums);
 }
 
 // ------------------------------------------------------------------------- line index
@@ -151,7 +76,7 @@ __global__ __launch_bounds__(FA_NL) void fa_line_ends_kernel(const uint8_t *__re
     uint32_t mask = fa_line_end_mask16(bytes, off, nbytes);
     const u64 c = __popc(mask);
     u64 total;
-    const u64 inc = fa_block_scan<FA_NL>(c, s_part, &total);
+    const u64 inc = scan_block<FA_NL>(c, s_part, &total);
     long long slot = (long long)(block_base[blockIdx.x] + inc - c);
     while (mask) {
         const int b = __ffs((int)mask) - 1;
@@ -293,7 +218,7 @@ FaWork fa_work(void *work, long long nbytes, long long nlines) {
     const long long nblk = fa_blocks(nbytes, FA_NL_BYTES);
     w.counts = (u64 *)(p + o); o += fa_align((size_t)nblk * 8);
     w.base = (u64 *)(p + o); o += fa_align((size_t)(nblk + 1) * 8);
-    w.csums = (u64 *)(p + o); o += fa_align((size_t)fa_blocks(nblk, FA_SCAN) * 8 + 8);
+    w.csums = (u64 *)(p + o); o += fa_align((size_t)fa_blocks(nblk, SCAN_BLOCK) * 8 + 8);
     w.cls = (uint8_t *)(p + o); o += fa_align((size_t)nlines);
     w.at = (uint32_t *)(p + o); o += fa_align((size_t)nlines * 4);
     w.len = (uint32_t *)(p + o); o += fa_align((size_t)nlines * 4);
@@ -301,7 +226,7 @@ FaWork fa_work(void *work, long long nbytes, long long nlines) {
     w.value = (u64 *)(p + o); o += fa_align((size_t)nlines * 8);
     w.pre = (u64 *)(p + o); o += fa_align((size_t)(nlines + 1) * 8);
     w.tail_pre = (u64 *)(p + o); o += fa_align((size_t)(nlines + 1) * 8);
-    w.sums = (u64 *)(p + o); o += fa_align((size_t)fa_blocks(nlines, FA_SCAN) * 8 + 8);
+    w.sums = (u64 *)(p + o); o += fa_align((size_t)fa_blocks(nlines, SCAN_BLOCK) * 8 + 8);
     w.bytes = o + 256;
     return w;
 }
@@ -324,7 +249,7 @@ int atr_fasta_scan(const uint8_t *d_bytes, int64_t nbytes, uint32_t *d_line_ends
                    int64_t *d_info, void *stream) {
     if (nbytes < 0 || nbytes >= (int64_t)0xFFFFFFF0ll || nlines < 0 || nlines > nbytes || !d_info) return ATR_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(fa_set_kernel, dim3(1), dim3(1), 0, st, (long long *)d_info + 2, (long long)LLONG_MAX);
+    hipLaunchKernelGGL(scan_set_kernel, dim3(1), dim3(1), 0, st, (long long *)d_info + 2, (long long)LLONG_MAX);
     if (nlines == 0) {
         hipError_t e = hipMemsetAsync(d_info, 0, 16, st);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
@@ -335,18 +260,18 @@ int atr_fasta_scan(const uint8_t *d_bytes, int64_t nbytes, uint32_t *d_line_ends
     const long long nblk = fa_blocks(nbytes, FA_NL_BYTES);
     // (the blocks' line counts: atr_fastq_count_lines keeps its own to itself)
     hipLaunchKernelGGL(fa_count_kernel, dim3((unsigned)nblk), dim3(FA_NL), 0, st, d_bytes, (long long)nbytes, w.counts);
-    fa_scan(w.counts, nblk, w.base, w.csums, st);
+    device_scan(w.counts, nblk, w.base, w.csums, st);
     hipLaunchKernelGGL(fa_line_ends_kernel, dim3((unsigned)nblk), dim3(FA_NL), 0, st, d_bytes, (long long)nbytes,
                        (const u64 *)w.base, (long long)nlines, d_line_ends);
     hipLaunchKernelGGL(fa_classify_kernel, dim3(fa_grid256(nlines)), dim3(256), 0, st, d_bytes, (const uint32_t *)d_line_ends,
                        (long long)nlines, w.cls, w.at, w.len, w.value);
-    fa_scan(w.value, nlines, w.pre, w.sums, st);
+    device_scan(w.value, nlines, w.pre, w.sums, st);
     hipLaunchKernelGGL(fa_heads_kernel, dim3(fa_grid256(nlines)), dim3(256), 0, st, (const uint8_t *)w.cls, (const u64 *)w.pre,
                        (long long)nlines, w.head_line, (u64 *)d_info + 2);
     hipLaunchKernelGGL(fa_gather_sizes_kernel, dim3(fa_grid256(nlines)), dim3(256), 0, st, (const uint32_t *)d_line_ends,
                        (const uint8_t *)w.cls, (const uint32_t *)w.at, (const uint32_t *)w.len, (const u64 *)w.pre,
                        (const uint32_t *)w.head_line, (long long)nlines, w.value);
-    fa_scan(w.value, nlines, w.tail_pre, w.sums, st);
+    device_scan(w.value, nlines, w.tail_pre, w.sums, st);
     hipLaunchKernelGGL(fa_info_kernel, dim3(1), dim3(1), 0, st, (const u64 *)w.pre, (const u64 *)w.tail_pre, (long long)nlines,
                        (long long *)d_info);
     return fa_launched("fasta scan launch");
@@ -377,7 +302,7 @@ int atr_fasta_index(uint8_t *d_bytes, int64_t nbytes, const uint32_t *d_line_end
 // work layout: [sizes u64 x n][sums u64 x blocks]
 size_t atr_fasta_emit_work_bytes(int64_t n) {
     if (n < 0) return 0;
-    return fa_align((size_t)n * 8) + fa_align((size_t)fa_blocks(n, FA_SCAN) * 8 + 8) + 256;
+    return fa_align((size_t)n * 8) + fa_align((size_t)fa_blocks(n, SCAN_BLOCK) * 8 + 8) + 256;
 }
 
 int atr_fasta_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, const int32_t *d_begin,
@@ -388,7 +313,7 @@ int atr_fasta_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, co
     if (n < 0 || !d_offsets || ((d_unmasked_begin == nullptr) != (d_unmasked_end == nullptr))) return ATR_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        if (!d_out) hipLaunchKernelGGL(fa_set_kernel, dim3(1), dim3(1), 0, st, (long long *)d_offsets, 0ll);
+        if (!d_out) hipLaunchKernelGGL(scan_set_kernel, dim3(1), dim3(1), 0, st, (long long *)d_offsets, 0ll);
         return fa_launched("fasta emit launch");
     }
     if (!d_bytes || !d_records || !d_begin || !d_end || !d_work) return ATR_ERR_INVALID;
@@ -397,7 +322,7 @@ int atr_fasta_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, co
         u64 *sums = (u64 *)((char *)d_work + fa_align((size_t)n * 8));
         hipLaunchKernelGGL(fa_emit_sizes_kernel, dim3(fa_grid256(n)), dim3(256), 0, st, (const FastqRecord *)d_records, d_begin,
                            d_end, d_dest, dest, (long long)n, sizes);
-        fa_scan(sizes, n, (u64 *)d_offsets, sums, st);
+        device_scan(sizes, n, (u64 *)d_offsets, sums, st);
         return fa_launched("fasta emit sizes launch");
     }
     hipLaunchKernelGGL(fa_emit_kernel, dim3((unsigned)fa_blocks(n * FA_EMIT_LANES, 256)), dim3(256), 0, st, d_bytes,

@@ -235,6 +235,14 @@ def guess_format(path):
     return None
 
 
+def file_format(path):
+    """"bam" for a name that ends in ``.bam`` (any letter case, no compression suffix: BAM is BGZF inside), else what
+    ``guess_format`` says -- ``.sam``, ``.bam.gz`` and colorspace FASTA stay its NotImplementedError."""
+    if str(path).lower().endswith(".bam"):
+        return "bam"
+    return guess_format(path)
+
+
 def sniff_format(head):
     """"fasta" if the first line of ``head`` (bytes) that is neither blank nor a '#' line begins with '>', else
     "fastq" -- what every input was before FASTA was read (a FASTQ file that begins with '>' is a FormatError either
@@ -247,14 +255,14 @@ def sniff_format(head):
 
 
 def input_format(path, explicit=None):
-    """The format a file is read as: ``explicit`` ("fasta" | "fastq"), else what its name says (``guess_format``),
-    else what its first byte says once it is decompressed and blank and '#' lines are passed (``sniff_format``; the
-    reference raises UnknownFileType for every name it does not know)."""
+    """The format a file is read as: ``explicit`` ("fasta" | "fastq" | "bam"), else what its name says
+    (``file_format``), else what its first byte says once it is decompressed and blank and '#' lines are passed
+    (``sniff_format``; the reference raises UnknownFileType for every name it does not know)."""
     if explicit is not None:
-        if explicit not in ("fasta", "fastq"):
-            raise ValueError("input_format must be 'fasta' or 'fastq'")
+        if explicit not in ("fasta", "fastq", "bam"):
+            raise ValueError("input_format must be 'fasta', 'fastq' or 'bam'")
         return explicit
-    fmt = guess_format(path)
+    fmt = file_format(path)
     if fmt is not None:
         return fmt
     name = str(path)
@@ -518,6 +526,14 @@ class ChunkedFastqReader(object):
     starts at their ``end_bit``), keeps the last 32 KiB of text as the next call's window and checks CRC-32 and ISIZE at
     a member's end.  A chunk holds at least one deflate block.
 
+    Unaligned BAM (``fmt == "bam"``: a name ending in ``.bam``, or ``input_format="bam"``) is a BGZF stream and always takes
+    the BGZF road above, whatever ``device_gunzip`` says; ``inflate_path == "device"``.  The chunk then holds BAM bytes: the
+    header, parsed once on the host, is skipped, the records are found by ``bam_walk`` and decoded to FASTQ text by
+    ``bam_to_fastq``, and the batch is ``FastqBatch.from_device`` over that text.  ``consumed`` and the
+    carry are BAM bytes.  ``paired``: records 2i and 2i + 1 are the reads of a pair (one name, read 1 / read 2 flags, read 2
+    first is swapped); a chunk's last record without partner waits in the carry, the file's is dropped.  A record the
+    reference fails on is a ``FormatError`` naming its number in the file and its name.
+
     ``byte_range`` = (lo, hi): only these bytes of a plain file, which must be whole records (a rank's shard,
     ``shard.fastq_shard_ranges``).  The loop that drives a reader -- ``next_batch``, ``advance``, ``close``, and two
     readers in lock step -- is ``read_chunks``; nothing else constructs one."""
@@ -527,14 +543,20 @@ class ChunkedFastqReader(object):
 
     BGZF_SCAN = 4096                                         # members per bgzf_scan call
 
-    def __init__(self, path, chunk_bytes, backend=None, clock=None, byte_range=None, device_gunzip=False, input_format=None):
+    def __init__(self, path, chunk_bytes, backend=None, clock=None, byte_range=None, device_gunzip=False, input_format=None,
+                 paired=False):
         name = str(path)
-        # "fasta" | "fastq": given, else by the file's name, else (None until the first chunk is there) by its first byte
-        self.fmt = input_format if input_format is not None else guess_format(name)
-        if self.fmt not in ("fasta", "fastq", None):
-            raise ValueError("input_format must be 'fasta' or 'fastq'")
+        # "fasta" | "fastq" | "bam": given, else by the file's name, else (None until the first chunk is there) by its
+        # first byte
+        self.fmt = input_format if input_format is not None else file_format(name)
+        if self.fmt not in ("fasta", "fastq", "bam", None):
+            raise ValueError("input_format must be 'fasta', 'fastq' or 'bam'")
         if self.fmt == "fasta" and byte_range is not None:
             raise NotImplementedError("a byte range of FASTA input is not provided")
+        if self.fmt == "bam" and byte_range is not None:
+            raise NotImplementedError("a byte range of BAM input is not provided")
+        is_bam = self.fmt == "bam"
+        self.paired = bool(paired)                            # (BAM: records 2i, 2i + 1 are decoded as the reads of a pair)
         if byte_range is not None and name.endswith((".gz", ".bz2", ".xz")):
             raise ValueError("a byte range of compressed input: the offsets are those of the plain text")
         self.be = backend or _lib.get_backend()
@@ -548,9 +570,10 @@ class ChunkedFastqReader(object):
         self.pos, self.size = byte_range or (0, os.path.getsize(path))      # (plain files: the next pread, the end)
         self.stream = None
         self.inflate_path = "host" if name.endswith(".gz") else None
-        self.any_gzip = device_gunzip == "any"
+        self.any_gzip = device_gunzip == "any" and not is_bam
         # (bgzf: the device road -- next_batch, advance, close; gz_stream: its chunks come from _assemble_stream)
-        self.bgzf = bool(device_gunzip and name.endswith(".gz") and self._starts_with_bgzf())
+        # BAM is BGZF by definition and always takes the device road: device_gunzip is about .gz
+        self.bgzf = is_bam or bool(device_gunzip and name.endswith(".gz") and self._starts_with_bgzf())
         self.gz_stream = bool(self.any_gzip and name.endswith(".gz") and not self.bgzf)
         if self.bgzf:
             self.inflate_path = "device"
@@ -585,6 +608,8 @@ class ChunkedFastqReader(object):
             self.uploaded = [None] * len(self.buf)
             self.data = None
             try:
+                if is_bam:
+                    self._bam_begin()
                 if self.gz_stream:
                     self._stream_begin(0)
                 for _ in range(0 if self.gz_stream else self.READ_AHEAD):
@@ -785,7 +810,7 @@ class ChunkedFastqReader(object):
             first = int(torch.nonzero(status)[0].item())
             raise gzip.BadGzipFile("BGZF member at file offset %d fails its checks (status %d of inflate_core.hpp)"
                                    % (pos + member_at[first], int(status[first].item())))
-        unterminated = bool(self.final and nbytes and int(data[nbytes - 1].item()) not in (10, 13))
+        unterminated = bool(self.fmt != "bam" and self.final and nbytes and int(data[nbytes - 1].item()) not in (10, 13))
         if unterminated:
             data[nbytes] = 10                                 # tolerate a missing last newline (_seqio.pyx:240-243)
             nbytes += 1
@@ -793,6 +818,88 @@ class ChunkedFastqReader(object):
                 self.upload_stream.wait_stream(torch.cuda.current_stream(self.be.device))
         self.data, self.nbytes = data, nbytes
         return data, nbytes, unterminated
+
+    # ---- unaligned BAM: the header on the host, the records walked and decoded to FASTQ text on the device
+    def _bam_begin(self):
+        """The header, inflated from the file's first members with zlib and parsed (``bam_header``): its bytes are
+        skipped in the chunks that hold them (``bam_skip``; it may be longer than a chunk)."""
+        import gzip
+        import zlib
+        text, pos, need = b"", 0, 12
+        while True:
+            raw = os.pread(self.fd, 1 << 20, pos)
+            head = torch.frombuffer(bytearray(raw), dtype=torch.uint8) if raw else None
+            m_at, _, k, covered, ok = self.be.bgzf_scan(head, 0, len(raw), self.BGZF_SCAN) if raw else (None, None, 0, 0, True)
+            if not k:
+                if not ok:
+                    raise gzip.BadGzipFile("not a BGZF member at file offset %d (BAM is a BGZF stream)" % pos)
+                raise FormatError("the BAM file ends inside its header" if text else "not a BAM file: no BGZF member")
+            at = [int(v) for v in m_at[:k + 1].tolist()]
+            for m in range(k):
+                try:
+                    text += zlib.decompress(raw[at[m]:at[m + 1]], 31)
+                except zlib.error as exc:
+                    raise gzip.BadGzipFile("BGZF member at file offset %d fails its checks (%s)" % (pos + at[m], exc))
+                if len(text) >= 8 and need == 12:
+                    if text[:4] != b"BAM\1":
+                        raise FormatError("not a BAM file: it begins with %r" % text[:4])
+                    need = 12 + max(int.from_bytes(text[4:8], "little", signed=True), 0)
+                if len(text) < need:
+                    continue
+                try:
+                    parsed = self.be.bam_header(text)
+                except ValueError:
+                    raise FormatError("not a BAM file: its header is malformed")
+                if parsed is not None:
+                    self.bam_skip, self.n_ref = parsed        # header bytes not yet passed; references of the header
+                    self.bam_records = 0                      # records handed out so far (error messages count from 1)
+                    return
+            pos += covered
+
+    def _bam_name(self, data, at, nbytes):
+        at = int(at)
+        if at + 36 > nbytes:
+            return "?"
+        end = min(at + 36 + max(int(data[at + 12].item()) - 1, 0), nbytes)
+        return _text(bytes(data[at + 36:end].cpu().numpy().tobytes()))
+
+    def _index_bam(self, data, nbytes):
+        """Walk + decode of a chunk of BAM bytes: the batch over the decoded FASTQ text, and the BAM bytes consumed."""
+        be = self.be
+        entry = min(self.bam_skip, nbytes)
+        self.bam_skip -= entry
+        if self.bam_skip and self.final:
+            raise FormatError("the BAM file ends inside its header")
+        starts, result = be.bam_walk(data, nbytes, entry, self.n_ref, self.final)
+        count, consumed, err, _repaired = (int(v) for v in result.cpu().tolist())
+        if err != _lib.INT64_MAX:
+            at, kind = err // 8, err % 8
+            what = {_lib.BAM_ERR_SMALL: "its block_size is smaller than its own fields need",
+                    _lib.BAM_ERR_BIG: "its block_size is above %d" % _lib.BAM_MAX_BLOCK,
+                    _lib.BAM_ERR_LSEQ: "its l_seq is negative",
+                    _lib.BAM_ERR_TRUNCATED: "the file ends inside it"}[kind]
+            name = "?" if kind in (_lib.BAM_ERR_SMALL, _lib.BAM_ERR_BIG) else self._bam_name(data, at, nbytes)
+            raise FormatError("BAM record %d (%r): %s" % (self.bam_records + count + 1, name, what))
+        if self.paired and count % 2:
+            count -= 1                                        # the file's last record without partner is dropped (zip(sam, sam))
+            if not self.final:
+                consumed = int(starts[count].item()) & 0xFFFFFFFF     # (a chunk's: it waits for its partner in the carry)
+        text, total, used, err, _ = be.bam_to_fastq(data, nbytes, starts, count, self.paired)
+        if err != _lib.INT64_MAX:
+            j, kind = err // 8, err % 8
+            number = self.bam_records + j + 1
+            name = self._bam_name(data, int(starts[j].item()) & 0xFFFFFFFF, nbytes)
+            if kind == _lib.BAM_REC_PAIR_NAME:                # io/seqio.py:627-632
+                other = self._bam_name(data, int(starts[j + 1].item()) & 0xFFFFFFFF, nbytes)
+                raise FormatError("BAM records %d and %d: Consecutive reads %s, %s in paired-end SAM/BAM file do not have the same "
+                                  "name; make sure your file is name-sorted and does not contain any secondary/supplementary "
+                                  "alignments." % (number, number + 1, name, other))
+            what = {_lib.BAM_REC_LSEQ0: "it has no sequence", _lib.BAM_REC_QUAL: "it has no qualities, or one above 93",
+                    _lib.BAM_REC_NAME: "its name holds a line end, or it has none",
+                    _lib.BAM_REC_PAIR_FLAGS: "it and the record behind it are not flagged as read 1 and read 2 of a pair"}[kind]
+            raise FormatError("BAM record %d (%r): %s" % (number, name, what))
+        self.bam_records += used
+        return FastqBatch.from_device(text, total, True, be)[0], consumed
 
     # ---- any other .gz input (device_gunzip="any"): member by member, slab by slab, inflated speculatively on the device
     # compressed bytes per speculative start (atr_gunzip_stream): the one serial wave resolves 32 KiB of text per
@@ -1012,6 +1119,8 @@ class ChunkedFastqReader(object):
 
     def _index(self, data, nbytes, unterminated, host=None):
         """The batch of the chunk's whole records in the file's format (its first chunk decides an unknown one)."""
+        if self.fmt == "bam":
+            return self._index_bam(data, nbytes)
         if self.fmt is None:
             head = host[:min(nbytes, 1 << 16)] if host is not None else data[:min(nbytes, 1 << 16)].cpu()
             self.fmt = sniff_format(head.numpy().tobytes())
@@ -1111,9 +1220,11 @@ def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, 
     two reads are not compared -- the two-file readers do not compare them either.  With ``byte_ranges`` it is a
     ValueError: a range may begin at a read 2.
 
-    ``input_formats``: "fasta" | "fastq" | None per path; None is the file's name, else its first byte
+    ``input_formats``: "fasta" | "fastq" | "bam" | None per path; None is the file's name, else its first byte
     (``input_format``).  FASTA paths yield ``FastaBatch``es; two paths of different formats are a ValueError, FASTA with
-    ``byte_ranges`` or ``interleaved`` a NotImplementedError."""
+    ``byte_ranges`` or ``interleaved`` a NotImplementedError.  A BAM path yields ``FastqBatch``es over the decoded text;
+    with ``interleaved`` the reader pairs the records itself (names and flags are checked, a last record without partner is
+    dropped: ``PairedEndSAMReader``); two BAM paths and BAM with ``byte_ranges`` are a NotImplementedError."""
     mismatch = "the two input files hold different numbers of records"
     if interleaved:
         if len(paths) != 1:
@@ -1123,7 +1234,10 @@ def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, 
     readers = []
     try:
         for path, byte_range, fmt in zip(paths, byte_ranges or [None] * len(paths), input_formats or [None] * len(paths)):
-            readers.append(ChunkedFastqReader(path, chunk_bytes, backend, clock, byte_range, device_gunzip, fmt))
+            readers.append(ChunkedFastqReader(path, chunk_bytes, backend, clock, byte_range, device_gunzip, fmt, interleaved))
+        if len(readers) > 1 and all(r.fmt == "bam" for r in readers):
+            raise NotImplementedError("two BAM files as the reads of a pair are not provided: one name-sorted BAM file "
+                                      "holds both (interleaved)")
         while True:
             batches = [r.next_batch() for r in readers]
             if len({r.fmt for r in readers}) > 1:

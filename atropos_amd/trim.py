@@ -296,6 +296,12 @@ class TrimFormats(object):
             raise ValueError("the two input files are of different formats (%s)" % " and ".join(self.inputs))
         self.fasta = fasta = self.inputs[0] == "fasta"
         paired = _is_paired(pipe)
+        if self.inputs[0] == "bam":
+            if len(paths_in) > 1:
+                raise NotImplementedError("two BAM files as the reads of a pair are not provided: one name-sorted BAM "
+                                          "file holds both (trim_files(path, None, ...), -l)")
+            if byte_ranges is not None and any(r is not None for r in byte_ranges):
+                raise NotImplementedError("a byte range of BAM input is not provided")
         demux = pipe_demultiplexes(pipe, paths_out, merged_out)
         if fasta:
             refuse_for_fasta(pipe)
@@ -958,7 +964,11 @@ class TrimPipeline(object):
         .fna (a compression suffix aside), else when its first byte is '>' (``fastq.input_format``).  The output is
         FASTA when its name says so, FASTQ when its name says so, and what the input is otherwise (``output_format``);
         the same goes for the too-short / too-long / untrimmed files.  FASTA input into a FASTQ-named file, and the
-        options that need qualities (``refuse_for_fasta``), are refused before any file is opened."""
+        options that need qualities (``refuse_for_fasta``), are refused before any file is opened.
+
+        Unaligned BAM: a name that ends in .bam (or ``input_format`` = "bam") is inflated, walked and decoded to FASTQ
+        text on the GPU (``fastq.ChunkedFastqReader``), whatever ``device_gunzip`` says; everything else works as on
+        FASTQ.  BAM / SAM output and SAM text input are a NotImplementedError before any file is opened."""
         if device_gzip and ("{name}" in path_out or self.demultiplex):
             raise NotImplementedError("device_gzip with demultiplexed outputs ({name} in the output path)")
         if "{name}" not in path_out and not self.demultiplex:
@@ -1478,7 +1488,10 @@ def pipeline_from_args(argv, paired_input=False, report=False):
     ap.add_argument("-w", "--overwrite-low-quality", default=None)
     ap.add_argument("-l", "--interleaved-input", default=None)
     ap.add_argument("-L", "--interleaved-output", default=None)
+    ap.add_argument("--input-read", type=int, choices=(0, 1, 2), default=0)
     o = ap.parse_args(argv)
+    if o.input_read:
+        raise NotImplementedError("--input-read 1 | 2 (one read of the pairs of a SAM / BAM file) is not provided")
     paired_input = bool(paired_input or o.interleaved_input)              # (-l is paired input, cli.py:614-618)
     overwrite = None
     if o.overwrite_low_quality:                                           # three comma-separated ints (cli.py:284-291)

@@ -1012,6 +1012,62 @@ int atr_fasta_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, co
                    const uint8_t *d_dest, int dest, int64_t n, int record_bytes_hint, int64_t *d_offsets, void *d_work,
                    uint8_t *d_out, void *stream);
 
+/* ---- unaligned BAM input (bam_kernels.hip, bam_core.hpp) ---------------------------------------------------------------
+ * The inflated bytes of a BAM stream (the BGZF members go through atr_gunzip_members): a header, then records of
+ * `block_size` (int32) + block_size bytes each (SAM/BAM specification, section 4.2).
+ *   atr_bam_header    HOST bytes: "BAM\1", l_text, the text, n_ref and the reference entries at the front of
+ *                     buf[0 .. n_bytes).  ATR_OK with *header_bytes and *n_ref; ATR_BAM_NEED_MORE when the buffer ends
+ *                     inside the header; ATR_ERR_INVALID for another magic or a negative length.
+ *   atr_bam_walk      DEVICE: d_bam[0 .. n_bytes) (16-byte aligned, readable up to the next multiple of 16 beyond
+ *                     n_bytes; no byte at or beyond n_bytes is read), `entry` the offset of a true record start (the
+ *                     header's end, 0 for a chunk that begins with a carried-over tail).  d_starts[0 .. count): the
+ *                     ascending starts of every WHOLE record, exactly what the serial walk  at += 4 + block_size  from
+ *                     entry gives for any byte content (slots at or beyond starts_capacity are not stored: (n_bytes -
+ *                     entry) / 36 + 1 holds every table).  The walk stops at the first record that is not whole or
+ *                     that is none.  d_result: 4 int64 DEVICE words -- count; consumed (the end of the last whole
+ *                     record); the error word offset * 8 + ATR_BAM_ERR_* of the record the walk stopped at, INT64_MAX
+ *                     if it merely ran out of bytes (with `final` set, bytes left over are ATR_BAM_ERR_TRUNCATED);
+ *                     the tiles whose speculative result had to be repaired.  The bytes are cut into tiles of
+ *                     tile_bytes (ATR_BAM_MIN_TILE .. ATR_BAM_MAX_TILE), each walked speculatively from the first
+ *                     offset at which a plausible record chain begins (n_ref bounds the reference ids of one); one
+ *                     serial pass over the TILES confirms or repairs them.  max_block: the largest block_size that is
+ *                     no error (32 .. INT32_MAX).  d_workspace: atr_bam_walk_workspace(n_bytes, tile_bytes) bytes.
+ *   atr_bam_to_fastq  DEVICE: '@' name '\n' SEQ '\n' '+' '\n' QUAL '\n' of records d_starts[0 .. n): the name without its
+ *                     NUL, the bases from the nibbles through "=ACMGRSVTWYHKDBN", every quality byte + 33 (SAMReader.
+ *                     _as_sequence then FastqFormat, io/seqio.py:580-585; no strand flip, no filtering by flag).
+ *                     paired: records 2i and 2i + 1 are a pair (PairedEndSAMReader, :618-640) -- equal names; the first
+ *                     has flag 0x40 and the second 0x80, or the second has 0x40 and the two are written in swapped
+ *                     order; a last record without partner is left out (d_result[2]: records written).  Two calls,
+ *                     as atr_fasta_emit: d_out NULL fills d_offsets[0 .. used] (exclusive prefix sum of the texts'
+ *                     sizes, by output slot) and d_result[0] = d_offsets[used]; the second call writes d_out.
+ *                     d_result[1]: the smallest ordinal * 8 + ATR_BAM_REC_* among the records that the reference
+ *                     fails on, INT64_MAX if none; the first call sees l_seq == 0, l_read_name == 0 and the pairs'
+ *                     names and flags, the second call '\n' / '\r' in a name and quality bytes above 93 (0xFF, "no
+ *                     qualities", among them) and leaves the word of the first call in place.  d_work:
+ *                     atr_bam_to_fastq_work_bytes(n) bytes.
+ * ATR_ERR_UNSUPPORTED before any pointer is looked at: n_bytes >= 2^32 - 16 (walk); n_bytes >= 2^31 - 16 (decode: a
+ * record's text is at most twice its bytes, and text tensors stay below 4 GiB).  Equal input gives equal results. */
+#define ATR_BAM_NEED_MORE 1
+#define ATR_BAM_MIN_TILE 64
+#define ATR_BAM_MAX_TILE (1 << 24)
+#define ATR_BAM_ERR_SMALL 1        /* block_size below 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq */
+#define ATR_BAM_ERR_BIG 2          /* block_size above max_block */
+#define ATR_BAM_ERR_LSEQ 3         /* negative l_seq */
+#define ATR_BAM_ERR_TRUNCATED 4    /* final: bytes behind the last whole record */
+#define ATR_BAM_REC_LSEQ0 1        /* no sequence (the reference has None) */
+#define ATR_BAM_REC_QUAL 2         /* a quality byte above 93 */
+#define ATR_BAM_REC_NAME 3         /* a line end in the name, or no name field at all */
+#define ATR_BAM_REC_PAIR_NAME 4    /* the two records of a pair are named differently */
+#define ATR_BAM_REC_PAIR_FLAGS 5   /* read 1 / read 2 flags of a pair */
+int atr_bam_header(const uint8_t *buf, int64_t n_bytes, int64_t *header_bytes, int32_t *n_ref);
+int64_t atr_bam_walk_workspace(int64_t n_bytes, int64_t tile_bytes);
+int atr_bam_walk(const uint8_t *d_bam, int64_t n_bytes, int64_t entry, int32_t n_ref, int final, int64_t tile_bytes,
+                 int64_t max_block, uint32_t *d_starts, int64_t starts_capacity, int64_t *d_result, void *d_workspace,
+                 int64_t workspace_bytes, void *stream);
+size_t atr_bam_to_fastq_work_bytes(int64_t n);
+int atr_bam_to_fastq(const uint8_t *d_bam, int64_t n_bytes, const uint32_t *d_starts, int64_t n, int paired, int64_t *d_offsets,
+                     int64_t *d_result, void *d_work, uint8_t *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
