@@ -8,10 +8,11 @@ surviving records are formatted on the device (``atr_fastq_emit``).  No per-read
 object exists anywhere on this path.
 """
 import collections
+import importlib
 import os
 import struct
 import time
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import Future, ThreadPoolExecutor
 from contextlib import ExitStack
 
 import torch
@@ -215,6 +216,23 @@ FASTA_SPACE = b" \t\n\r\x0b\x0c\x1c\x1d\x1e\x1f"        # what the FASTA index s
 _COMPRESSED = (".gz", ".bz2", ".xz")
 
 
+def _codec(path):
+    """The module that reads and writes a compressed file, by the name's suffix as the reference's xopen chooses it;
+    None for any other name."""
+    name = str(path)
+    for sfx, module in zip(_COMPRESSED, ("gzip", "bz2", "lzma")):
+        if name.endswith(sfx):
+            return importlib.import_module(module)
+    return None
+
+
+def open_compressed(path, file=None):
+    """The decompressed bytes of a ``.gz`` / ``.bz2`` / ``.xz`` file for reading (``file``: the open file to read them
+    from), None for any other name."""
+    mod = _codec(path)
+    return mod.open(file if file is not None else str(path), "rb") if mod else None
+
+
 def guess_format(path):
     """"fasta", "fastq" or None (unknown) from a file name, its compression suffix aside: the reference's
     ``guess_format_from_name`` over ``splitext_compressed`` (io/seqio.py:958-989).  The formats it knows and this
@@ -265,16 +283,7 @@ def input_format(path, explicit=None):
     fmt = file_format(path)
     if fmt is not None:
         return fmt
-    name = str(path)
-    if name.endswith(".gz"):
-        import gzip as mod
-    elif name.endswith(".bz2"):
-        import bz2 as mod
-    elif name.endswith(".xz"):
-        import lzma as mod
-    else:
-        mod = None
-    with (mod.open(name, "rb") if mod else open(name, "rb")) as fh:
+    with (open_compressed(path) or open(str(path), "rb")) as fh:
         return sniff_format(fh.read(1 << 16))
 
 
@@ -492,11 +501,190 @@ class _NotBgzf(Exception):
         self.offset = offset
 
 
-class ChunkedFastqReader(object):
-    """Feeds a FASTQ file to the GPU in chunks of whole records.  The file is read straight into
-    page-locked staging buffers (``IO_THREADS`` ``pread`` slices per chunk, no intermediate bytes objects).
+# What a source hands out.  ``data``: the device tensor (zero behind ``nbytes``, padded to 16 bytes and 16 more);
+# ``host``: the same bytes in the staging buffer, on the roads whose text passes through it; ``unterminated``: the
+# file's last newline was missing and has been supplied; ``ready`` / ``keep``: the event behind the upload and the
+# tensors the upload stream allocated (``_ChunkIO.claim``).
+Chunk = collections.namedtuple("Chunk", "data nbytes final host unterminated ready keep")
 
-    Plain files: ``READ_AHEAD`` chunks are being READ while the GPU works on the current one.  What a chunk
+
+def _settled(result=None, error=None):
+    """A future that is done: a source's ``pending`` is a future of a Chunk on every road, and a failure met while the
+    chunk was put together is raised by its ``result()``, when the chunk is asked for."""
+    fut = Future()
+    if error is not None:
+        fut.set_exception(error)
+    else:
+        fut.set_result(result)
+    return fut
+
+
+class _ChunkIO(object):
+    """What the input roads of a reader share, each written once: the file and its size, the page-locked staging
+    buffers and whose turn it is, the ``pread`` pool and the read-ahead thread, the upload stream, the clock."""
+
+    def __init__(self, path, backend, clock, chunk_bytes, limits):
+        self.file = open(path, "rb")
+        self.fd, self.size = self.file.fileno(), os.fstat(self.file.fileno()).st_size
+        self.be, self.clock, self.chunk_bytes = backend, clock, chunk_bytes
+        self.limits = limits                                  # the reader: READ_AHEAD, RESERVE, BGZF_SCAN, STREAM_SPACING
+        self.pinned = getattr(backend, "name", "") == "hip"
+        self.buf, self.uploaded, self.next_slot = [], [], 0
+        self.readers = self.ahead = self.upload_stream = None
+
+    def allocate(self, nbuf):
+        """The staging buffers (a chunk and the reserve for the carry in front of it) and the threads of a road."""
+        for _ in range(nbuf):
+            self.buf.append(_staging(self.chunk_bytes + self.limits.RESERVE + 32, self.pinned))
+        self.uploaded = [None] * nbuf                         # per staging buffer: the event behind its last upload
+        self.readers = ThreadPoolExecutor(IO_THREADS)
+        self.ahead = ThreadPoolExecutor(1)
+        # the host -> device copy of a chunk runs on its own stream: it overlaps the GPU work on the chunk before
+        self.upload_stream = torch.cuda.Stream(device=self.be.device) if self.pinned else None
+
+    def read(self, view, offset, want):
+        """Starts reading the file's bytes [offset, offset + want) into ``view``, a slice per thread of the pool;
+        ``finish`` waits for them."""
+        step = ((want + IO_THREADS - 1) // IO_THREADS + 4095) & ~4095
+        jobs = []
+        for t in range(IO_THREADS):
+            lo, hi = t * step, min(want, (t + 1) * step)
+            if hi > lo:
+                jobs.append(self.readers.submit(os.preadv, self.fd, [view[lo:hi]], offset + lo))
+        return jobs, want
+
+    def finish(self, read):
+        jobs, want = read
+        if sum(j.result() for j in jobs) != want:
+            raise IOError("short read: the input file changed while it was being read")
+        return want
+
+    def take_slot(self):
+        """The staging buffer whose turn it is, once the upload that last read it has landed (chunks ago: long gone)."""
+        slot = self.next_slot
+        self.next_slot = (slot + 1) % len(self.buf)
+        if self.uploaded[slot] is not None:
+            self.uploaded[slot].synchronize()
+            self.uploaded[slot] = None
+        return slot
+
+    def on_upload_stream(self):
+        """A context: the upload stream, where the run has one (the CPU twins have none)."""
+        stack = ExitStack()
+        if self.upload_stream is not None:
+            stack.enter_context(torch.cuda.device(self.be.device))
+            stack.enter_context(torch.cuda.stream(self.upload_stream))
+        return stack
+
+    def to_device(self, host, n, pad=16):
+        """``host[:n]`` in a new device tensor of ``n`` rounded up to 16, and ``pad``, bytes: zero behind ``n``."""
+        data = self.be.empty(((n + 15) // 16 * 16 + pad,), torch.uint8)
+        data[:n].copy_(host[:n], non_blocking=True)
+        data[n:].zero_()
+        return data
+
+    def mark(self, slot):
+        """(on the upload stream) The event behind what was queued so far: staging buffer ``slot`` is free after it."""
+        ready = None
+        if self.upload_stream is not None:
+            ready = torch.cuda.Event()
+            ready.record()
+        self.uploaded[slot] = ready
+        return ready
+
+    def host_chunk(self, slot, host, nbytes, final, lines):
+        """The chunk of [carry | new bytes] as they stand in ``host``, a view of staging buffer ``slot``: its upload is
+        started; a missing last newline of the file is tolerated (_seqio.pyx:240-243) where the decoder reads ``lines``."""
+        unterminated = bool(lines and final and nbytes and int(host[nbytes - 1]) not in (10, 13))
+        if unterminated:
+            host[nbytes] = 10
+            nbytes += 1
+        with self.on_upload_stream():
+            data, ready = self.to_device(host, nbytes), self.mark(slot)
+        return Chunk(data, nbytes, final, host, unterminated, ready, (data,))
+
+    def starts_with_bgzf(self):
+        head = torch.frombuffer(bytearray(os.pread(self.fd, 65536, 0)), dtype=torch.uint8) if self.size else None
+        return head is not None and self.be.bgzf_scan(head, 0, head.numel(), 1)[4]
+
+    def claim(self, chunk):
+        """The caller's stream waits for the chunk's upload and takes over the tensors the upload stream allocated."""
+        if chunk.ready is not None:
+            with torch.cuda.device(self.be.device):
+                cur = torch.cuda.current_stream()
+                cur.wait_event(chunk.ready)
+                for t in chunk.keep:
+                    if t is not None:
+                        t.record_stream(cur)
+
+    def close(self):
+        for pool in (self.readers, self.ahead):
+            if pool is not None:
+                pool.shutdown()                               # (waits: reads and slabs still in flight own their buffers)
+        for ev in self.uploaded:
+            if ev is not None:
+                ev.synchronize()
+        self.file.close()
+        _release(self.buf)
+        self.buf = []
+
+
+def _end_last_line_on_device(io, chunk, lines):
+    """A missing last newline is tolerated (_seqio.pyx:240-243) in a chunk inflated on the device as well (in a staging
+    buffer: ``_ChunkIO.host_chunk``), on the caller's stream, where the decoder reads ``lines``."""
+    data, nbytes = chunk.data, chunk.nbytes
+    if not (lines and chunk.final and nbytes and int(data[nbytes - 1].item()) not in (10, 13)):
+        return chunk
+    data[nbytes] = 10
+    if chunk.ready is not None:                               # (the carry is copied on the upload stream)
+        io.upload_stream.wait_stream(torch.cuda.current_stream(io.be.device))
+    return chunk._replace(nbytes=nbytes + 1, unterminated=True)
+
+
+class _Source(object):
+    """One input road of a reader.  ``pending`` is a future of the next Chunk (``_settled``); ``take`` makes it the
+    current one on the caller's stream; ``advance`` puts the one after it together behind what the caller left;
+    ``close`` drains what the source has in flight on the read-ahead thread (``_ChunkIO.close`` then waits for the
+    ``pread`` pool and the uploads).  ``lines``: the decoder reads lines of text, so a missing last newline is
+    supplied."""
+
+    inflate_path = None
+
+    def __init__(self, io, lines):
+        self.io, self.lines = io, lines
+        self.pending = self.chunk = None
+
+    def carry(self, consumed):
+        """What the caller left of the current chunk, to stand in front of the next one (None at the start: nothing):
+        ``bytes`` on the roads that put a chunk together in a staging buffer."""
+        return bytes(self.chunk.host[consumed:self.chunk.nbytes].numpy().tobytes())
+
+    def take(self, chunk):
+        self.io.claim(chunk)
+        self.chunk = chunk
+        return chunk
+
+    def advance(self, consumed):
+        """-> the source of the next chunk: this one, one that takes over from it, or None: the file is exhausted and
+        nothing is carried over."""
+        if self.chunk.final and consumed == self.chunk.nbytes:
+            return None
+        return self.prepare(self.carry(consumed))
+
+    def close(self):
+        pass
+
+
+class _DeviceSource(_Source):
+    """The roads that put a chunk together on the device: the carry is (tensor, lo, hi), a slice of the current chunk
+    that is copied device to device -- the text never visits the host."""
+
+    def carry(self, consumed):
+        return self.chunk.data, consumed, self.chunk.nbytes
+
+
+class _PlainSource(_Source):
+    """Plain files: ``READ_AHEAD`` chunks are being READ while the GPU works on the current one.  What a chunk
     carries over from the one before it (its unfinished last record; in a paired run the surplus records of the
     file with the smaller records) is known only once that chunk has been indexed on the device, but the file
     READ does not depend on it: the new bytes land behind a reserve at the front of the staging buffer, the
@@ -505,225 +693,127 @@ class ChunkedFastqReader(object):
     chain, the upload engine idle during every read (the "upload_and_index" wait of ``trim_file``): 16 M x 150 bp
     into eight part files 64 -> 107 M reads/s.  (A producer thread that also INDEXES each chunk on the upload stream, so
     that the next upload starts a record count after the last, was measured next: 96 M -- its index kernels and its
-    Python run against the caller's -- and is not kept.)
+    Python run against the caller's -- and is not kept.)  ``byte_range``: only these bytes of the file."""
 
-    ``.gz`` / ``.bz2`` / ``.xz`` input (what the reference's xopen opens by extension) is decompressed by one
-    read-ahead thread straight into the staging buffer: the decompressor then sets the pace.
+    def __init__(self, io, lines, byte_range):
+        _Source.__init__(self, io, lines)
+        self.pos, self.end = byte_range or (0, io.size)       # the next pread, the end
+        self.reads = collections.deque()                      # (slot, pread jobs and bytes asked for, last chunk of the file)
+        self.read_done = False
+        self.carry_est = 0
+        io.allocate(io.limits.READ_AHEAD + 1)
+        for _ in range(io.limits.READ_AHEAD):
+            self._issue_read()
 
-    ``device_gunzip=True`` and a ``.gz`` file whose first member is BGZF (what ``bgzip``, htslib and ``device_gzip=True``
-    write: members of at most 64 KiB that carry their own size): the COMPRESSED bytes take the plain-file road -- slabs
-    read ahead with the ``pread`` pool and walked member by member on the host (``bgzf_scan``), a job that never waits
-    for the GPU -- and are inflated on the device (``gunzip_members``, a wave per member) straight into the chunk's text
-    tensor behind the carried-over tail, which is a device-to-device copy: the text never visits the host.
-    ``inflate_path`` says which road a reader took: "device", "host" (any other ``.gz``: unchanged), or None.  The flag
-    wants BGZF throughout: a later member that is not BGZF, or one that fails its checks, is a ``gzip.BadGzipFile``
-    naming the member's file offset; a file that ends inside a member is an ``EOFError``.
-
-    ``device_gunzip="any"``: every other ``.gz`` member -- an ordinary gzip file, and an ordinary member behind BGZF ones,
-    which ``True`` refuses -- is inflated on the device as well (``gunzip_stream``: the deflate stream split
-    speculatively; ``inflate_path == "stream"``).  The host parses the member headers, issues one call per
-    slab of compressed bytes into the chunk's text tensor, reads the call's eight result words back (the next call
-    starts at their ``end_bit``), keeps the last 32 KiB of text as the next call's window and checks CRC-32 and ISIZE at
-    a member's end.  A chunk holds at least one deflate block.
-
-    Unaligned BAM (``fmt == "bam"``: a name ending in ``.bam``, or ``input_format="bam"``) is a BGZF stream and always takes
-    the BGZF road above, whatever ``device_gunzip`` says; ``inflate_path == "device"``.  The chunk then holds BAM bytes: the
-    header, parsed once on the host, is skipped, the records are found by ``bam_walk`` and decoded to FASTQ text by
-    ``bam_to_fastq``, and the batch is ``FastqBatch.from_device`` over that text.  ``consumed`` and the
-    carry are BAM bytes.  ``paired``: records 2i and 2i + 1 are the reads of a pair (one name, read 1 / read 2 flags, read 2
-    first is swapped); a chunk's last record without partner waits in the carry, the file's is dropped.  A record the
-    reference fails on is a ``FormatError`` naming its number in the file and its name.
-
-    ``byte_range`` = (lo, hi): only these bytes of a plain file, which must be whole records (a rank's shard,
-    ``shard.fastq_shard_ranges``).  The loop that drives a reader -- ``next_batch``, ``advance``, ``close``, and two
-    readers in lock step -- is ``read_chunks``; nothing else constructs one."""
-
-    READ_AHEAD = 3
-    RESERVE = 64 << 20                                       # room for the carried-over tail of the previous chunk
-
-    BGZF_SCAN = 4096                                         # members per bgzf_scan call
-
-    def __init__(self, path, chunk_bytes, backend=None, clock=None, byte_range=None, device_gunzip=False, input_format=None,
-                 paired=False):
-        name = str(path)
-        # "fasta" | "fastq" | "bam": given, else by the file's name, else (None until the first chunk is there) by its
-        # first byte
-        self.fmt = input_format if input_format is not None else file_format(name)
-        if self.fmt not in ("fasta", "fastq", "bam", None):
-            raise ValueError("input_format must be 'fasta', 'fastq' or 'bam'")
-        if self.fmt == "fasta" and byte_range is not None:
-            raise NotImplementedError("a byte range of FASTA input is not provided")
-        if self.fmt == "bam" and byte_range is not None:
-            raise NotImplementedError("a byte range of BAM input is not provided")
-        is_bam = self.fmt == "bam"
-        self.paired = bool(paired)                            # (BAM: records 2i, 2i + 1 are decoded as the reads of a pair)
-        if byte_range is not None and name.endswith((".gz", ".bz2", ".xz")):
-            raise ValueError("a byte range of compressed input: the offsets are those of the plain text")
-        self.be = backend or _lib.get_backend()
-        self.byte_range = byte_range
-        self.clock = clock or StageClock()
-        self.chunk_bytes = int(chunk_bytes)
-        cap = self.chunk_bytes + self.RESERVE
-        pinned = getattr(self.be, "name", "") == "hip"
-        self.file = open(path, "rb")
-        self.fd = self.file.fileno()
-        self.pos, self.size = byte_range or (0, os.path.getsize(path))      # (plain files: the next pread, the end)
-        self.stream = None
-        self.inflate_path = "host" if name.endswith(".gz") else None
-        self.any_gzip = device_gunzip == "any" and not is_bam
-        # (bgzf: the device road -- next_batch, advance, close; gz_stream: its chunks come from _assemble_stream)
-        # BAM is BGZF by definition and always takes the device road: device_gunzip is about .gz
-        self.bgzf = is_bam or bool(device_gunzip and name.endswith(".gz") and self._starts_with_bgzf())
-        self.gz_stream = bool(self.any_gzip and name.endswith(".gz") and not self.bgzf)
-        if self.bgzf:
-            self.inflate_path = "device"
-        elif self.gz_stream:
-            self.bgzf = True
-            self.inflate_path = "stream"
-        elif name.endswith(".gz"):
-            import gzip
-            self.stream = gzip.open(self.file, "rb")
-        elif name.endswith(".bz2"):
-            import bz2
-            self.stream = bz2.open(self.file, "rb")
-        elif name.endswith(".xz"):
-            import lzma
-            self.stream = lzma.open(self.file, "rb")
-        self.buf = [_staging(cap + 32, pinned) for _ in range(2 if self.stream is not None else self.READ_AHEAD + 1)]
-        self.readers = ThreadPoolExecutor(IO_THREADS)
-        self.ahead = ThreadPoolExecutor(1)
-        self.k = 0
-        # the host -> device copy of a chunk runs on its own stream: it overlaps the GPU work on the chunk before
-        self.upload_stream = torch.cuda.Stream(device=self.be.device) if pinned else None
-        self.host = None
-        self.nbytes = 0
-        self.final = False
-        if self.stream is not None:
-            self.pending = self.ahead.submit(self._fill, 0, b"")
-        elif self.bgzf:
-            self.reads = collections.deque()                 # futures of _read_slab
-            self.next_slot = 0
-            self.carry_est = 0
-            self.ratio = 1.0                                 # compressed bytes per byte of text, as last seen
-            self.uploaded = [None] * len(self.buf)
-            self.data = None
-            try:
-                if is_bam:
-                    self._bam_begin()
-                if self.gz_stream:
-                    self._stream_begin(0)
-                for _ in range(0 if self.gz_stream else self.READ_AHEAD):
-                    self.reads.append(self.ahead.submit(self._read_slab))
-                self.pending = self._assemble_device(None)
-            except BaseException:
-                self.close()                                  # (nobody else holds the file and the two thread pools yet)
-                raise
-        else:
-            self.reads = collections.deque()                 # (slot, pread jobs, bytes asked for, last chunk of the file)
-            self.next_slot = 0
-            self.read_done = False
-            self.carry_est = 0
-            self.uploaded = [None] * len(self.buf)           # per staging buffer: the event behind its last upload
-            for _ in range(self.READ_AHEAD):
-                self._issue_read()
-            self.pending = self._assemble(b"")
-
-    # ---- plain files: reads ahead of the carry
     def _issue_read(self):
         if self.read_done:
             return
-        slot = self.next_slot
-        self.next_slot = (slot + 1) % len(self.buf)
-        if self.uploaded[slot] is not None:
-            self.uploaded[slot].synchronize()                # (three chunks ago: long gone)
-            self.uploaded[slot] = None
+        io = self.io
+        slot = io.take_slot()                                 # (three chunks ago: long gone)
         # a chunk is carry + new bytes ~ chunk_bytes in all: in a paired run the file with the smaller records
         # carries its surplus records over every time, and reading a full chunk on top of it would let that
         # surplus grow without bound (1 % of a chunk per step for records 1 % apart).  The carry of the chunk
         # this read will follow is not known yet; the last one seen stands in for it (it drifts slowly).
-        want = max(self.chunk_bytes - self.carry_est, self.chunk_bytes // 4)
-        want = min(want, self.size - self.pos)
-        view = memoryview(self.buf[slot].numpy())
-        step = ((want + IO_THREADS - 1) // IO_THREADS + 4095) & ~4095
-        jobs = []
-        for t in range(IO_THREADS):
-            lo, hi = t * step, min(want, (t + 1) * step)
-            if hi > lo:
-                jobs.append(self.readers.submit(os.preadv, self.fd, [view[self.RESERVE + lo:self.RESERVE + hi]], self.pos + lo))
+        want = max(io.chunk_bytes - self.carry_est, io.chunk_bytes // 4)
+        want = min(want, self.end - self.pos)
+        read = io.read(memoryview(io.buf[slot].numpy())[io.limits.RESERVE:], self.pos, want)
         self.pos += want
-        self.read_done = self.pos >= self.size
-        self.reads.append((slot, jobs, want, self.read_done))
+        self.read_done = self.pos >= self.end
+        self.reads.append((slot, read, self.read_done))
 
-    def _assemble(self, carry):
+    def prepare(self, carry):
         """The next chunk: its carried-over head in front of the bytes read for it, and its upload."""
+        io, reserve = self.io, self.io.limits.RESERVE
         t0 = time.perf_counter()
         if self.reads:
-            slot, jobs, want, final = self.reads.popleft()
-            got = sum(j.result() for j in jobs)
-            if got != want:
-                raise IOError("short read: the input file changed while it was being read")
+            slot, read, final = self.reads.popleft()
+            got = io.finish(read)
         else:                                                 # the file is read; records carried over are left
-            slot, got, final = self.next_slot, 0, True
-            self.next_slot = (slot + 1) % len(self.buf)
-            if self.uploaded[slot] is not None:
-                self.uploaded[slot].synchronize()
-                self.uploaded[slot] = None
-        self.clock.add("wait_file_read", t0)
-        n0 = len(carry)
-        if n0 > self.RESERVE:
+            slot, got, final = io.take_slot(), 0, True
+        io.clock.add("wait_file_read", t0)
+        n0 = len(carry or b"")
+        if n0 > reserve:
             raise ValueError("%d bytes carried over from one chunk to the next (a FASTQ record, or the surplus records of "
-                             "one file of a pair, of more than %d bytes)" % (n0, self.RESERVE))
-        start = self.RESERVE - n0
-        host = self.buf[slot][start:]
+                             "one file of a pair, of more than %d bytes)" % (n0, reserve))
+        host = io.buf[slot][reserve - n0:]
         if n0:
             memoryview(host.numpy())[:n0] = carry
         self.carry_est = n0
-        nbytes = n0 + got
-        unterminated = bool(final and nbytes and int(host[nbytes - 1]) not in (10, 13))
-        if unterminated:
-            host[nbytes] = 10                                 # tolerate a missing last newline (_seqio.pyx:240-243)
-            nbytes += 1
-        data = ready = None
-        if self.upload_stream is not None:
-            with torch.cuda.device(self.be.device), torch.cuda.stream(self.upload_stream):
-                data = torch.empty(((nbytes + 15) // 16 * 16 + 16,), dtype=torch.uint8, device=self.be.device)
-                data[:nbytes].copy_(host[:nbytes], non_blocking=True)
-                data[nbytes:].zero_()
-                ready = torch.cuda.Event()
-                ready.record()
-            self.uploaded[slot] = ready
+        self.pending = _settled(io.host_chunk(slot, host, n0 + got, final, self.lines))
         self._issue_read()                                    # the buffer of the chunk before this one is free again
-        return nbytes, final, unterminated, data, ready, host
+        return self
 
-    # ---- BGZF input: compressed slabs read and scanned ahead, inflated on the device
-    def _starts_with_bgzf(self):
-        head = torch.frombuffer(bytearray(os.pread(self.fd, 65536, 0)), dtype=torch.uint8) if self.size else None
-        return head is not None and self.be.bgzf_scan(head, 0, head.numel(), 1)[4]
+
+class _DecompressedSource(_Source):
+    """``.gz`` / ``.bz2`` / ``.xz`` input (what the reference's xopen opens by extension) is decompressed by one
+    read-ahead thread straight into the staging buffer, one chunk ahead: the decompressor then sets the pace."""
+
+    def __init__(self, io, lines, stream, inflate_path):
+        _Source.__init__(self, io, lines)
+        self.stream, self.inflate_path = stream, inflate_path
+        io.allocate(2)
+
+    def prepare(self, carry):
+        self.pending = self.io.ahead.submit(self._fill, carry)
+        return self
+
+    def _fill(self, carry):
+        io = self.io
+        slot = io.take_slot()
+        host = io.buf[slot]
+        view = memoryview(host.numpy())
+        n0 = len(carry or b"")
+        if n0:
+            view[:n0] = carry
+        room = host.numel() - 32 - n0
+        want = max(io.chunk_bytes - n0, min(io.chunk_bytes // 4, room))
+        if want <= 0:
+            raise ValueError("FASTQ record of more than %d bytes" % host.numel())
+        want, got = min(want, room), 0
+        while got < want:
+            n = self.stream.readinto(view[n0 + got:n0 + want])
+            if not n:
+                break
+            got += n
+        return io.host_chunk(slot, host, n0 + got, got < want, self.lines)
+
+
+class _BgzfSource(_DeviceSource):
+    """BGZF input (what ``bgzip``, htslib and ``device_gzip=True`` write: members of at most 64 KiB that carry their own
+    size): the COMPRESSED bytes take the plain-file road -- slabs read ahead with the ``pread`` pool and walked member by
+    member on the host (``bgzf_scan``), a job that never waits for the GPU -- and are inflated on the device
+    (``gunzip_members``, a wave per member) straight into the chunk's text tensor behind the carried-over tail, which is
+    a device-to-device copy.  A member that fails its checks is a ``gzip.BadGzipFile`` naming its file offset, a file
+    that ends inside a member an ``EOFError``; a member that is not BGZF is a ``BadGzipFile`` too, unless ``any_gzip``:
+    then a ``_GzipStreamSource`` takes over at its offset."""
+
+    inflate_path = "device"
+
+    def __init__(self, io, lines, any_gzip):
+        _Source.__init__(self, io, lines)
+        self.any_gzip = any_gzip
+        self.pos = 0                                          # the next slab's file offset
+        self.reads = collections.deque()                      # futures of _read_slab
+        self.carry_est = 0
+        self.ratio = 1.0                                      # compressed bytes per byte of text, as last seen
+        self.members = None                                   # of the pending chunk: status, bad, file offset, member offsets
+        io.allocate(io.limits.READ_AHEAD + 1)
+        for _ in range(io.limits.READ_AHEAD):
+            self.reads.append(io.ahead.submit(self._read_slab))
 
     def _read_slab(self):
         """(read-ahead thread) The next slab of compressed bytes and its whole members, as many as hold the text of
         a chunk.  Nothing here waits for the GPU but the reuse of a staging buffer three chunks later."""
-        slot = self.next_slot
-        self.next_slot = (slot + 1) % len(self.buf)
-        if self.uploaded[slot] is not None:
-            self.uploaded[slot].synchronize()
-            self.uploaded[slot] = None
-        budget = max(self.chunk_bytes - self.carry_est, self.chunk_bytes // 4)
-        room = self.buf[slot].numel() - 32
-        want = min(self.size - self.pos, room, max(int(budget * self.ratio * 1.25) + (128 << 10), 1 << 17))
-        view = memoryview(self.buf[slot].numpy())
-        step = ((want + IO_THREADS - 1) // IO_THREADS + 4095) & ~4095
-        jobs = []
-        for t in range(IO_THREADS):
-            lo, hi = t * step, min(want, (t + 1) * step)
-            if hi > lo:
-                jobs.append(self.readers.submit(os.preadv, self.fd, [view[lo:hi]], self.pos + lo))
-        if sum(j.result() for j in jobs) != want:
-            raise IOError("short read: the input file changed while it was being read")
-        at_end = self.pos + want >= self.size
+        io, scan = self.io, self.io.limits.BGZF_SCAN
+        slot = io.take_slot()
+        host = io.buf[slot]
+        budget = max(io.chunk_bytes - self.carry_est, io.chunk_bytes // 4)
+        want = min(io.size - self.pos, host.numel() - 32, max(int(budget * self.ratio * 1.25) + (128 << 10), 1 << 17))
+        io.finish(io.read(memoryview(host.numpy()), self.pos, want))
+        at_end = self.pos + want >= io.size
         member_at, text_at, k, covered, error = [0], [0], 0, 0, None
-        while covered < want and text_at[-1] <= budget and k + self.BGZF_SCAN <= _lib.GUNZIP_MAX_MEMBERS:
-            m_at, t_at, n, took, ok = self.be.bgzf_scan(self.buf[slot], covered, want, self.BGZF_SCAN)
+        while covered < want and text_at[-1] <= budget and k + scan <= _lib.GUNZIP_MAX_MEMBERS:
+            m_at, t_at, n, took, ok = io.be.bgzf_scan(host, covered, want, scan)
             member_at += [covered + v for v in m_at[1:n + 1].tolist()]
             text_at += [text_at[-1] + v for v in t_at[1:n + 1].tolist()]
             k += n
@@ -733,7 +823,7 @@ class ChunkedFastqReader(object):
             elif not ok:
                 import gzip
                 error = gzip.BadGzipFile("not a BGZF member at file offset %d (device_gunzip wants BGZF throughout)" % (self.pos + covered))
-            if not ok or n < self.BGZF_SCAN:
+            if not ok or n < scan:
                 break
         while k > 1 and text_at[k] > budget:                  # (members are taken while their text fits)
             k -= 1
@@ -748,88 +838,294 @@ class ChunkedFastqReader(object):
             self.ratio = covered / float(text_at[k])
         pos = self.pos
         self.pos += covered
-        return slot, pos, covered, member_at[:k + 1], text_at[:k + 1], self.pos >= self.size, error
+        return slot, pos, covered, member_at[:k + 1], text_at[:k + 1], self.pos >= io.size, error
 
-    def _assemble_device(self, carry):
+    def prepare(self, carry):
         """The next chunk: [carried-over text | the text of the next slab's members], both put there on the device."""
-        if self.gz_stream:
-            return self._assemble_stream(carry)
+        io, be = self.io, self.io.be
+        n0 = carry[2] - carry[1] if carry else 0
+        self.carry_est = n0
         t0 = time.perf_counter()
         slot, pos, n, member_at, text_at, final, error = self.reads.popleft().result()
-        self.clock.add("wait_file_read", t0)
+        io.clock.add("wait_file_read", t0)
         if isinstance(error, _NotBgzf):                       # an ordinary member behind BGZF members
-            for fut in self.reads:
-                fut.exception()
+            self.close()
             self.reads.clear()
-            self.gz_stream = True
-            self._stream_begin(error.offset)
-            return self._assemble_stream(carry)
+            return _GzipStreamSource(io, self.lines, error.offset, self.ratio).prepare(carry)
         if error is not None:
-            return error                                      # (raised when this chunk is asked for)
+            self.pending = _settled(error=error)              # (raised when this chunk is asked for)
+            return self
         k, total = len(member_at) - 1, text_at[-1]
-        n0 = carry[2] - carry[1] if carry else 0
         nbytes = n0 + total
-        host = self.buf[slot]
-        up = self.upload_stream
-        status = bad = ready = None
-        with ExitStack() as on_upload_stream:
-            if up is not None:
-                on_upload_stream.enter_context(torch.cuda.device(self.be.device))
-                on_upload_stream.enter_context(torch.cuda.stream(up))
-            data = self.be.empty(((nbytes + 15) // 16 * 16 + 16,), torch.uint8)
+        status = bad = None
+        with io.on_upload_stream():
+            data = be.empty(((nbytes + 15) // 16 * 16 + 16,), torch.uint8)
             if n0:
                 data[:n0].copy_(carry[0][carry[1]:carry[2]])
             if k:
-                comp = self.be.empty(((n + 15) // 16 * 16,), torch.uint8)
-                comp[:n].copy_(host[:n], non_blocking=True)
-                comp[n:].zero_()
-                offsets = torch.tensor([member_at, text_at], dtype=torch.int64).to(self.be.device)
-                status, bad = self.be.gunzip_members(comp, n, offsets[0], offsets[1], k, data[n0:], total)
+                comp = io.to_device(io.buf[slot], n, pad=0)
+                offsets = torch.tensor([member_at, text_at], dtype=torch.int64).to(be.device)
+                status, bad = be.gunzip_members(comp, n, offsets[0], offsets[1], k, data[n0:], total)
             data[nbytes:].zero_()
-            if up is not None:
-                ready = torch.cuda.Event()
-                ready.record()
-        self.uploaded[slot] = ready
-        self.reads.append(self.ahead.submit(self._read_slab))  # (past the end of the file: an empty, final slab)
-        return nbytes, final, data, ready, status, bad, pos, member_at
+            ready = io.mark(slot)
+        self.reads.append(io.ahead.submit(self._read_slab))   # (past the end of the file: an empty, final slab)
+        self.members = status, bad, pos, member_at
+        self.pending = _settled(Chunk(data, nbytes, final, None, False, ready, (data, status, bad)))
+        return self
 
-    def _next_device(self):
-        res = self.pending
-        if isinstance(res, BaseException):
-            raise res
-        nbytes, self.final, data, ready, status, bad, pos, member_at = res
-        if ready is not None:
-            with torch.cuda.device(self.be.device):
-                cur = torch.cuda.current_stream()
-                cur.wait_event(ready)
-                for t in (data, status, bad):
-                    if t is not None:
-                        t.record_stream(cur)
+    def take(self, chunk):
+        _Source.take(self, chunk)
+        status, bad, pos, member_at = self.members
         if bad is not None and int(bad.item()):
             import gzip
             first = int(torch.nonzero(status)[0].item())
             raise gzip.BadGzipFile("BGZF member at file offset %d fails its checks (status %d of inflate_core.hpp)"
                                    % (pos + member_at[first], int(status[first].item())))
-        unterminated = bool(self.fmt != "bam" and self.final and nbytes and int(data[nbytes - 1].item()) not in (10, 13))
-        if unterminated:
-            data[nbytes] = 10                                 # tolerate a missing last newline (_seqio.pyx:240-243)
-            nbytes += 1
-            if ready is not None:                             # (the carry is copied on the upload stream)
-                self.upload_stream.wait_stream(torch.cuda.current_stream(self.be.device))
-        self.data, self.nbytes = data, nbytes
-        return data, nbytes, unterminated
+        self.chunk = _end_last_line_on_device(self.io, chunk, self.lines)
+        return self.chunk
 
-    # ---- unaligned BAM: the header on the host, the records walked and decoded to FASTQ text on the device
-    def _bam_begin(self):
+    def close(self):
+        for fut in self.reads:
+            fut.exception()                                   # (a slab still being read owns its buffer)
+
+
+class _GzipStreamSource(_DeviceSource):
+    """Any other ``.gz`` member (``device_gunzip="any"``): an ordinary gzip file, or the rest of a file from an ordinary
+    member behind BGZF ones on (then the BGZF source's staging buffers, pools and last compression ratio are taken
+    over), inflated on the device member by member, slab by slab (``gunzip_stream``: the deflate stream split
+    speculatively).  The host parses the member headers, issues one call per slab of compressed bytes into
+    the chunk's text tensor, reads the call's eight result words back (the next call starts at their ``end_bit``), keeps
+    the last 32 KiB of text as the next call's window and checks CRC-32 and ISIZE at a member's end.  A chunk holds at
+    least one deflate block.  The slab is staging buffer 0; ``offset``: where a member's header stands (or the file
+    ends)."""
+
+    inflate_path = "stream"
+
+    def __init__(self, io, lines, offset, ratio):
+        _Source.__init__(self, io, lines)
+        if not io.buf:                                        # (else: taken over from a BGZF source, whose uploads have landed)
+            io.allocate(1)
+        self.ratio = ratio                                    # compressed bytes per byte of text, as last seen
+        self.pos = offset                                     # file offset of slab byte 0
+        self.n = 0                                            # bytes of the slab
+        self.at = 0                                           # next byte of the slab: a header, or (in a member) unused
+        self.dev = None                                       # the slab on the device
+        self.member = None                                    # file offset of the member being inflated
+        self.bit = 0                                          # ... and the bit of the slab its next block starts at
+        self.crc = self.isize = 0
+        self.window = io.be.empty((32768,), torch.uint8)
+        self.wlen = 0
+        self.work = None
+        self.done = False
+        # compressed bytes per speculative start: see ChunkedFastqReader.STREAM_SPACING
+        self.spacing = min(io.limits.STREAM_SPACING, max(256, io.chunk_bytes // 64))
+
+    def _load(self, start, want):
+        """Slab := the file's bytes [start, start + want), as far as the file goes."""
+        io = self.io
+        want = max(0, min(want, io.buf[0].numel() - 32, _lib.GUNZIP_STREAM_MAX, io.size - start))
+        io.finish(io.read(memoryview(io.buf[0].numpy()), start, want))
+        self.bit -= 8 * (start - self.pos)
+        self.at -= start - self.pos
+        self.pos, self.n, self.dev = start, want, None
+
+    def _more(self, keep_from, budget):
+        """A slab that begins at slab byte ``keep_from`` and is larger than what is left behind it; -> False at the file's end."""
+        if self.pos + self.n >= self.io.size:
+            return False
+        left = self.n - keep_from
+        self._load(self.pos + keep_from, max(2 * left, int(budget * self.ratio * 1.25) + (128 << 10)))
+        if self.n <= left:
+            raise ValueError("a deflate block or a gzip header of more than %d bytes at file offset %d" % (left, self.pos))
+        return True
+
+    def _header(self, buf, at, end, at_eof):
+        """The gzip member header at slab byte ``at``: -> the byte its deflate data starts at, or None: not all there.
+        What Python's gzip module refuses is refused with its exception."""
+        import gzip
+
+        def short():
+            if at_eof:
+                raise EOFError("Compressed file ended before the end-of-stream marker was reached")
+
+        if end - at < 2:
+            if at_eof:
+                raise gzip.BadGzipFile("Not a gzipped file (%r)" % bytes(buf[at:end]))
+            return None
+        if buf[at] != 0x1f or buf[at + 1] != 0x8b:
+            raise gzip.BadGzipFile("Not a gzipped file (%r) at file offset %d " % (bytes(buf[at:at + 2]), self.pos + at))
+        if end - at < 10:
+            return short()
+        if buf[at + 2] != 8:
+            raise gzip.BadGzipFile("Unknown compression method at file offset %d " % (self.pos + at))
+        flags, p = int(buf[at + 3]), at + 10
+        if flags & 4:                                         # FEXTRA
+            if end - p < 2:
+                return short()
+            p += 2 + int(buf[p]) + 256 * int(buf[p + 1])
+        for bit in (8, 16):                                   # FNAME, FCOMMENT: zero-terminated
+            if flags & bit:
+                while p < end and buf[p]:
+                    p += 1
+                p += 1
+        if flags & 2:                                         # FHCRC
+            p += 2
+        return p if p <= end else short()
+
+    def prepare(self, carry):
+        """The next chunk: [carried-over text | text of the members' blocks, as much as the chunk takes]."""
+        try:
+            self.pending = _settled(self._inflate(carry))
+        except Exception as e:                                # noqa: BLE001 (raised when this chunk is asked for)
+            self.pending = _settled(error=e)
+        return self
+
+    def _inflate(self, carry):
+        import gzip
+        import zlib
+        io, be = self.io, self.io.be
+        n0 = carry[2] - carry[1] if carry else 0
+        budget = max(io.chunk_bytes - n0, io.chunk_bytes // 4)
+        data = be.empty(((n0 + budget + 15) // 16 * 16 + 32,), torch.uint8)
+        if n0:
+            data[:n0].copy_(carry[0][carry[1]:carry[2]])
+        filled = 0
+        buf = io.buf[0].numpy()
+        while not self.done and filled < budget:
+            t0 = time.perf_counter()
+            at_eof = self.pos + self.n >= io.size
+            if self.member is None:                           # between members: zero padding, the end, or a header
+                while self.at < self.n and buf[self.at] == 0 and self.pos + self.at > 0:
+                    self.at += 1
+                if self.at >= self.n:
+                    if at_eof:
+                        self.done = True
+                        break
+                    self._load(self.pos + self.at, int(budget * self.ratio * 1.25) + (128 << 10))
+                    io.clock.add("wait_file_read", t0)
+                    continue
+                start = self._header(buf, self.at, self.n, at_eof)
+                if start is None:
+                    self._more(self.at, budget)
+                    io.clock.add("wait_file_read", t0)
+                    continue
+                self.member, self.bit = self.pos + self.at, 8 * start
+                self.crc = self.isize = self.wlen = 0
+            if self.dev is None:
+                self.dev = io.to_device(io.buf[0], self.n)
+            io.clock.add("wait_file_read", t0)
+            byte = self.bit // 8
+            room = budget - filled
+            need = be.gunzip_stream_workspace(self.n - byte, self.spacing, room)
+            if self.work is None or self.work.numel() < need:
+                self.work = be.empty((need,), torch.uint8)
+            res = be.gunzip_stream(self.dev[byte:], self.n - byte, self.bit - 8 * byte, self.window, self.wlen, self.crc,
+                                   data[n0 + filled:], room, self.spacing, work=self.work)
+            status, end_bit, got, final, crc = res.cpu().tolist()[:5]   # (the next call's first bit: the one wait of a call)
+            if status == _lib.GUNZIP_NEED_INPUT:
+                if not self._more(byte, budget):
+                    raise EOFError("Compressed file ended before the end-of-stream marker was reached")
+                continue
+            if status == _lib.GUNZIP_NEED_ROOM:
+                if filled:
+                    break                                     # (the next chunk has all its room for this block)
+                budget *= 2                                   # a block of more text than a chunk: this chunk grows
+                grown = be.empty(((n0 + budget + 15) // 16 * 16 + 32,), torch.uint8)
+                grown[:n0].copy_(data[:n0])
+                data = grown
+                continue
+            if status:                                        # (what the host road's decompressor raises for bad deflate data)
+                raise zlib.error("Error -3 while decompressing data: the gzip member at file offset %d breaks rule %d of "
+                                 "inflate_core.hpp" % (self.member, status))
+            if got:
+                lo = n0 + filled
+                if got >= 32768:
+                    self.window.copy_(data[lo + got - 32768:lo + got])
+                    self.wlen = 32768
+                else:
+                    both = torch.cat([self.window[:self.wlen], data[lo:lo + got]])[-32768:]
+                    self.wlen = both.numel()
+                    self.window[:self.wlen].copy_(both)
+                self.ratio = max(end_bit / 8.0 / got, 0.001)
+            filled += got
+            self.crc, self.isize = crc, (self.isize + got) & 0xffffffff
+            self.bit = 8 * byte + end_bit
+            if not final:
+                # the slab ended inside a block, or the next block's text does not fit: the next call says which, at
+                # the price of decoding the rest of the slab once more -- so a chunk that is half full ends here
+                if got < room and 2 * filled >= budget:
+                    break
+                if got < room and self.pos + self.n < io.size:
+                    self._more(self.bit // 8, budget)
+                continue
+            trailer = (self.bit + 7) // 8
+            if trailer + 8 > self.n:
+                if not self._more(self.bit // 8, budget):
+                    raise EOFError("Compressed file ended before the end-of-stream marker was reached")
+                trailer = (self.bit + 7) // 8
+                if trailer + 8 > self.n:
+                    raise EOFError("Compressed file ended before the end-of-stream marker was reached")
+            want_crc, want_size = struct.unpack("<II", bytes(buf[trailer:trailer + 8]))
+            if want_crc != self.crc:
+                raise gzip.BadGzipFile("CRC check failed for the gzip member at file offset %d (%#x != %#x)" % (self.member, want_crc, self.crc))
+            if want_size != self.isize:
+                raise gzip.BadGzipFile("Incorrect length of data produced by the gzip member at file offset %d " % self.member)
+            self.member, self.at = None, trailer + 8
+        nbytes = n0 + filled
+        data[nbytes:nbytes + 32].zero_()
+        return Chunk(data[:(nbytes + 15) // 16 * 16 + 16], nbytes, self.done, None, False, None, ())
+
+    def take(self, chunk):
+        self.chunk = _end_last_line_on_device(self.io, chunk, self.lines)
+        return self.chunk
+
+
+# ---- decoders: a chunk -> (the batch of its whole records, the bytes of the chunk they take)
+class _TextDecoder(object):
+    """FASTQ or FASTA text; the first chunk decides a format that neither the caller nor the file's name gave."""
+
+    lines = True
+
+    def __init__(self, fmt, byte_range, backend):
+        self.fmt, self.byte_range, self.be = fmt, byte_range, backend
+
+    def __call__(self, chunk):
+        if self.fmt is None:
+            n = min(chunk.nbytes, 1 << 16)
+            head = chunk.host[:n] if chunk.host is not None else chunk.data[:n].cpu()
+            self.fmt = sniff_format(head.numpy().tobytes())
+            if self.fmt == "fasta" and self.byte_range:
+                raise NotImplementedError("a byte range of FASTA input is not provided")
+        cls = FastaBatch if self.fmt == "fasta" else FastqBatch
+        return cls.from_device(chunk.data, chunk.nbytes, chunk.final, self.be, unterminated=chunk.unterminated)
+
+
+class _BamDecoder(object):
+    """Unaligned BAM over the chunks of a ``_BgzfSource``, which then hold BAM bytes: the header, parsed once on the
+    host, is skipped, the records are found by ``bam_walk`` and decoded to FASTQ text by ``bam_to_fastq`` (DESIGN
+    3.8i), and the batch is ``FastqBatch.from_device`` over that text.  ``consumed`` and the carry are BAM bytes.
+    ``paired``: records 2i and 2i + 1 are the reads of a pair (one name, read 1 / read 2 flags, read 2 first is
+    swapped); a chunk's last record without partner waits in the carry, the file's is dropped.  A record the reference
+    fails on is a ``FormatError`` naming its number in the file and its name."""
+
+    fmt = "bam"
+    lines = False
+
+    def __init__(self, io, paired):
+        self.be, self.paired = io.be, paired
+        self.skip, self.n_ref = self._header(io)              # header bytes not yet passed; references of the header
+        self.records = 0                                      # records handed out so far (error messages count from 1)
+
+    def _header(self, io):
         """The header, inflated from the file's first members with zlib and parsed (``bam_header``): its bytes are
-        skipped in the chunks that hold them (``bam_skip``; it may be longer than a chunk)."""
+        skipped in the chunks that hold them (it may be longer than a chunk)."""
         import gzip
         import zlib
         text, pos, need = b"", 0, 12
         while True:
-            raw = os.pread(self.fd, 1 << 20, pos)
+            raw = os.pread(io.fd, 1 << 20, pos)
             head = torch.frombuffer(bytearray(raw), dtype=torch.uint8) if raw else None
-            m_at, _, k, covered, ok = self.be.bgzf_scan(head, 0, len(raw), self.BGZF_SCAN) if raw else (None, None, 0, 0, True)
+            m_at, _, k, covered, ok = self.be.bgzf_scan(head, 0, len(raw), io.limits.BGZF_SCAN) if raw else (None, None, 0, 0, True)
             if not k:
                 if not ok:
                     raise gzip.BadGzipFile("not a BGZF member at file offset %d (BAM is a BGZF stream)" % pos)
@@ -851,26 +1147,24 @@ class ChunkedFastqReader(object):
                 except ValueError:
                     raise FormatError("not a BAM file: its header is malformed")
                 if parsed is not None:
-                    self.bam_skip, self.n_ref = parsed        # header bytes not yet passed; references of the header
-                    self.bam_records = 0                      # records handed out so far (error messages count from 1)
-                    return
+                    return parsed
             pos += covered
 
-    def _bam_name(self, data, at, nbytes):
+    def _name(self, data, at, nbytes):
         at = int(at)
         if at + 36 > nbytes:
             return "?"
         end = min(at + 36 + max(int(data[at + 12].item()) - 1, 0), nbytes)
         return _text(bytes(data[at + 36:end].cpu().numpy().tobytes()))
 
-    def _index_bam(self, data, nbytes):
+    def __call__(self, chunk):
         """Walk + decode of a chunk of BAM bytes: the batch over the decoded FASTQ text, and the BAM bytes consumed."""
-        be = self.be
-        entry = min(self.bam_skip, nbytes)
-        self.bam_skip -= entry
-        if self.bam_skip and self.final:
+        be, data, nbytes = self.be, chunk.data, chunk.nbytes
+        entry = min(self.skip, nbytes)
+        self.skip -= entry
+        if self.skip and chunk.final:
             raise FormatError("the BAM file ends inside its header")
-        starts, result = be.bam_walk(data, nbytes, entry, self.n_ref, self.final)
+        starts, result = be.bam_walk(data, nbytes, entry, self.n_ref, chunk.final)
         count, consumed, err, _repaired = (int(v) for v in result.cpu().tolist())
         if err != _lib.INT64_MAX:
             at, kind = err // 8, err % 8
@@ -878,19 +1172,19 @@ class ChunkedFastqReader(object):
                     _lib.BAM_ERR_BIG: "its block_size is above %d" % _lib.BAM_MAX_BLOCK,
                     _lib.BAM_ERR_LSEQ: "its l_seq is negative",
                     _lib.BAM_ERR_TRUNCATED: "the file ends inside it"}[kind]
-            name = "?" if kind in (_lib.BAM_ERR_SMALL, _lib.BAM_ERR_BIG) else self._bam_name(data, at, nbytes)
-            raise FormatError("BAM record %d (%r): %s" % (self.bam_records + count + 1, name, what))
+            name = "?" if kind in (_lib.BAM_ERR_SMALL, _lib.BAM_ERR_BIG) else self._name(data, at, nbytes)
+            raise FormatError("BAM record %d (%r): %s" % (self.records + count + 1, name, what))
         if self.paired and count % 2:
             count -= 1                                        # the file's last record without partner is dropped (zip(sam, sam))
-            if not self.final:
+            if not chunk.final:
                 consumed = int(starts[count].item()) & 0xFFFFFFFF     # (a chunk's: it waits for its partner in the carry)
         text, total, used, err, _ = be.bam_to_fastq(data, nbytes, starts, count, self.paired)
         if err != _lib.INT64_MAX:
             j, kind = err // 8, err % 8
-            number = self.bam_records + j + 1
-            name = self._bam_name(data, int(starts[j].item()) & 0xFFFFFFFF, nbytes)
+            number = self.records + j + 1
+            name = self._name(data, int(starts[j].item()) & 0xFFFFFFFF, nbytes)
             if kind == _lib.BAM_REC_PAIR_NAME:                # io/seqio.py:627-632
-                other = self._bam_name(data, int(starts[j + 1].item()) & 0xFFFFFFFF, nbytes)
+                other = self._name(data, int(starts[j + 1].item()) & 0xFFFFFFFF, nbytes)
                 raise FormatError("BAM records %d and %d: Consecutive reads %s, %s in paired-end SAM/BAM file do not have the same "
                                   "name; make sure your file is name-sorted and does not contain any secondary/supplementary "
                                   "alignments." % (number, number + 1, name, other))
@@ -898,261 +1192,102 @@ class ChunkedFastqReader(object):
                     _lib.BAM_REC_NAME: "its name holds a line end, or it has none",
                     _lib.BAM_REC_PAIR_FLAGS: "it and the record behind it are not flagged as read 1 and read 2 of a pair"}[kind]
             raise FormatError("BAM record %d (%r): %s" % (number, name, what))
-        self.bam_records += used
+        self.records += used
         return FastqBatch.from_device(text, total, True, be)[0], consumed
 
-    # ---- any other .gz input (device_gunzip="any"): member by member, slab by slab, inflated speculatively on the device
+
+class ChunkedFastqReader(object):
+    """Feeds a FASTQ, FASTA or unaligned BAM file to the GPU in chunks of whole records.  The file is read straight into
+    page-locked staging buffers (``IO_THREADS`` ``pread`` slices per chunk, no intermediate bytes objects).
+
+    The reader picks a SOURCE, which puts the chunks together, and a DECODER, which makes the batch of a chunk's whole
+    records; ``_ChunkIO`` holds what the sources share.  The sources, by the file's name and ``device_gunzip``:
+
+    ``_PlainSource``: plain files, read ``READ_AHEAD`` chunks ahead of the carry.  ``byte_range`` = (lo, hi): only
+    these bytes, which must be whole records (a rank's shard, ``shard.fastq_shard_ranges``).
+
+    ``_DecompressedSource``: ``.gz`` / ``.bz2`` / ``.xz`` through a host decompressor thread.
+
+    ``_BgzfSource``: ``device_gunzip=True`` and a ``.gz`` file whose first member is BGZF: the compressed slabs are read
+    ahead and inflated on the device; the text never visits the host.  The flag wants BGZF throughout: a later member
+    that is not BGZF, or one that fails its checks, is a ``gzip.BadGzipFile`` naming the member's file offset; a file
+    that ends inside a member is an ``EOFError``.
+
+    ``_GzipStreamSource``: ``device_gunzip="any"``: every other ``.gz`` member -- an ordinary gzip file, and an ordinary
+    member behind BGZF ones, which ``True`` refuses: there the BGZF source hands the rest of the file over to a stream
+    source -- is inflated on the device as well.
+
+    ``inflate_path`` says which source a reader STARTED with: "device" (BGZF), "stream", "host" (any other ``.gz``), or
+    None.
+
+    The decoders: ``_TextDecoder`` (FASTQ / FASTA; ``fmt`` is None until the first chunk has been sniffed, where neither
+    the caller nor the name says it) and ``_BamDecoder`` (``fmt == "bam"``: a name ending in ``.bam``, or
+    ``input_format="bam"``), which always sits on a ``_BgzfSource``, whatever ``device_gunzip`` says; ``paired`` tells
+    it that records 2i and 2i + 1 are the reads of a pair.
+
+    The loop that drives a reader -- ``next_batch``, ``advance``, ``close``, and two readers in lock step -- is
+    ``read_chunks``; nothing else constructs one."""
+
+    READ_AHEAD = 3
+    RESERVE = 64 << 20                                       # room for the carried-over tail of the previous chunk
+
+    BGZF_SCAN = 4096                                         # members per bgzf_scan call
+
     # compressed bytes per speculative start (atr_gunzip_stream): the one serial wave resolves 32 KiB of text per
     # confirmed chunk, so a chunk should hold many times that; 128 KiB is some 300 - 600 KB of FASTQ
     STREAM_SPACING = 131072
 
-    def _stream_begin(self, offset):
-        """The stream road from file offset ``offset`` on, where a member's header stands (or the file ends)."""
-        self.z_pos = offset                                   # file offset of slab byte 0
-        self.z_n = 0                                          # bytes of the slab (self.buf[0])
-        self.z_at = 0                                         # next byte of the slab: a header, or (in a member) unused
-        self.z_dev = None                                     # the slab on the device
-        self.z_member = None                                  # file offset of the member being inflated
-        self.z_bit = 0                                        # ... and the bit of the slab its next block starts at
-        self.z_crc = self.z_isize = 0
-        self.z_window = self.be.empty((32768,), torch.uint8)
-        self.z_wlen = 0
-        self.z_work = None
-        self.z_done = False
-        self.z_spacing = min(self.STREAM_SPACING, max(256, self.chunk_bytes // 64))
+    def __init__(self, path, chunk_bytes, backend=None, clock=None, byte_range=None, device_gunzip=False, input_format=None,
+                 paired=False):
+        name = str(path)
+        # "fasta" | "fastq" | "bam": given, else by the file's name, else (None until the first chunk is there) by its
+        # first byte
+        fmt = input_format if input_format is not None else file_format(name)
+        if fmt not in ("fasta", "fastq", "bam", None):
+            raise ValueError("input_format must be 'fasta', 'fastq' or 'bam'")
+        if fmt == "fasta" and byte_range is not None:
+            raise NotImplementedError("a byte range of FASTA input is not provided")
+        if fmt == "bam" and byte_range is not None:
+            raise NotImplementedError("a byte range of BAM input is not provided")
+        self.paired = bool(paired)                            # (BAM: records 2i, 2i + 1 are decoded as the reads of a pair)
+        if byte_range is not None and _codec(name):
+            raise ValueError("a byte range of compressed input: the offsets are those of the plain text")
+        be = backend or _lib.get_backend()
+        self.clock = clock or StageClock()
+        self.nbytes, self.final = 0, False
+        self.source = self.decoder = None
+        io = self.io = _ChunkIO(path, be, self.clock, int(chunk_bytes), self)
+        try:                                                  # (nobody else holds the file, the thread pools and the buffers yet)
+            self.decoder = _BamDecoder(io, self.paired) if fmt == "bam" else _TextDecoder(fmt, byte_range, be)
+            lines, gz = self.decoder.lines, name.endswith(".gz")
+            # BAM is BGZF by definition and always takes the device road: device_gunzip is about .gz
+            if fmt == "bam" or (device_gunzip and gz and io.starts_with_bgzf()):
+                source = _BgzfSource(io, lines, device_gunzip == "any" and fmt != "bam")
+            elif device_gunzip == "any" and gz:
+                source = _GzipStreamSource(io, lines, 0, 1.0)
+            elif _codec(name):
+                source = _DecompressedSource(io, lines, open_compressed(name, io.file), "host" if gz else None)
+            else:
+                source = _PlainSource(io, lines, byte_range)
+            self.inflate_path = source.inflate_path
+            self.source = source.prepare(None)
+        except BaseException:
+            self.close()
+            raise
 
-    def _stream_load(self, start, want):
-        """Slab := the file's bytes [start, start + want), as far as the file goes."""
-        want = max(0, min(want, self.buf[0].numel() - 32, _lib.GUNZIP_STREAM_MAX, self.size - start))
-        view = memoryview(self.buf[0].numpy())
-        step = ((want + IO_THREADS - 1) // IO_THREADS + 4095) & ~4095
-        jobs = []
-        for t in range(IO_THREADS):
-            lo, hi = t * step, min(want, (t + 1) * step)
-            if hi > lo:
-                jobs.append(self.readers.submit(os.preadv, self.fd, [view[lo:hi]], start + lo))
-        if sum(j.result() for j in jobs) != want:
-            raise IOError("short read: the input file changed while it was being read")
-        self.z_bit -= 8 * (start - self.z_pos)
-        self.z_at -= start - self.z_pos
-        self.z_pos, self.z_n, self.z_dev = start, want, None
-
-    def _stream_more(self, keep_from, budget):
-        """A slab that begins at slab byte ``keep_from`` and is larger than what is left behind it; -> False at the file's end."""
-        if self.z_pos + self.z_n >= self.size:
-            return False
-        left = self.z_n - keep_from
-        self._stream_load(self.z_pos + keep_from, max(2 * left, int(budget * self.ratio * 1.25) + (128 << 10)))
-        if self.z_n <= left:
-            raise ValueError("a deflate block or a gzip header of more than %d bytes at file offset %d" % (left, self.z_pos))
-        return True
-
-    def _stream_header(self, buf, at, end, at_eof):
-        """The gzip member header at slab byte ``at``: -> the byte its deflate data starts at, or None: not all there.
-        What Python's gzip module refuses is refused with its exception."""
-        import gzip
-
-        def short():
-            if at_eof:
-                raise EOFError("Compressed file ended before the end-of-stream marker was reached")
-
-        if end - at < 2:
-            if at_eof:
-                raise gzip.BadGzipFile("Not a gzipped file (%r)" % bytes(buf[at:end]))
-            return None
-        if buf[at] != 0x1f or buf[at + 1] != 0x8b:
-            raise gzip.BadGzipFile("Not a gzipped file (%r) at file offset %d " % (bytes(buf[at:at + 2]), self.z_pos + at))
-        if end - at < 10:
-            return short()
-        if buf[at + 2] != 8:
-            raise gzip.BadGzipFile("Unknown compression method at file offset %d " % (self.z_pos + at))
-        flags, p = int(buf[at + 3]), at + 10
-        if flags & 4:                                         # FEXTRA
-            if end - p < 2:
-                return short()
-            p += 2 + int(buf[p]) + 256 * int(buf[p + 1])
-        for bit in (8, 16):                                   # FNAME, FCOMMENT: zero-terminated
-            if flags & bit:
-                while p < end and buf[p]:
-                    p += 1
-                p += 1
-        if flags & 2:                                         # FHCRC
-            p += 2
-        return p if p <= end else short()
-
-    def _assemble_stream(self, carry):
-        """The next chunk: [carried-over text | text of the members' blocks, as much as the chunk takes]."""
-        try:
-            return self._assemble_stream_or_raise(carry)
-        except Exception as e:                                # noqa: BLE001 (raised when this chunk is asked for)
-            return e
-
-    def _assemble_stream_or_raise(self, carry):
-        import gzip
-        import zlib
-        be = self.be
-        n0 = carry[2] - carry[1] if carry else 0
-        budget = max(self.chunk_bytes - n0, self.chunk_bytes // 4)
-        data = be.empty(((n0 + budget + 15) // 16 * 16 + 32,), torch.uint8)
-        if n0:
-            data[:n0].copy_(carry[0][carry[1]:carry[2]])
-        filled = 0
-        buf = self.buf[0].numpy()
-        while not self.z_done and filled < budget:
-            t0 = time.perf_counter()
-            at_eof = self.z_pos + self.z_n >= self.size
-            if self.z_member is None:                         # between members: zero padding, the end, or a header
-                while self.z_at < self.z_n and buf[self.z_at] == 0 and self.z_pos + self.z_at > 0:
-                    self.z_at += 1
-                if self.z_at >= self.z_n:
-                    if at_eof:
-                        self.z_done = True
-                        break
-                    self._stream_load(self.z_pos + self.z_at, int(budget * self.ratio * 1.25) + (128 << 10))
-                    self.clock.add("wait_file_read", t0)
-                    continue
-                start = self._stream_header(buf, self.z_at, self.z_n, at_eof)
-                if start is None:
-                    self._stream_more(self.z_at, budget)
-                    self.clock.add("wait_file_read", t0)
-                    continue
-                self.z_member, self.z_bit = self.z_pos + self.z_at, 8 * start
-                self.z_crc = self.z_isize = self.z_wlen = 0
-            if self.z_dev is None:
-                n = self.z_n
-                self.z_dev = be.empty(((n + 15) // 16 * 16 + 16,), torch.uint8)
-                self.z_dev[:n].copy_(self.buf[0][:n], non_blocking=True)
-                self.z_dev[n:].zero_()
-            self.clock.add("wait_file_read", t0)
-            byte = self.z_bit // 8
-            room = budget - filled
-            need = be.gunzip_stream_workspace(self.z_n - byte, self.z_spacing, room)
-            if self.z_work is None or self.z_work.numel() < need:
-                self.z_work = be.empty((need,), torch.uint8)
-            res = be.gunzip_stream(self.z_dev[byte:], self.z_n - byte, self.z_bit - 8 * byte, self.z_window, self.z_wlen, self.z_crc,
-                                   data[n0 + filled:], room, self.z_spacing, work=self.z_work)
-            status, end_bit, got, final, crc = res.cpu().tolist()[:5]   # (the next call's first bit: the one wait of a call)
-            if status == _lib.GUNZIP_NEED_INPUT:
-                if not self._stream_more(byte, budget):
-                    raise EOFError("Compressed file ended before the end-of-stream marker was reached")
-                continue
-            if status == _lib.GUNZIP_NEED_ROOM:
-                if filled:
-                    break                                     # (the next chunk has all its room for this block)
-                budget *= 2                                   # a block of more text than a chunk: this chunk grows
-                grown = be.empty(((n0 + budget + 15) // 16 * 16 + 32,), torch.uint8)
-                grown[:n0].copy_(data[:n0])
-                data = grown
-                continue
-            if status:                                        # (what the host road's decompressor raises for bad deflate data)
-                raise zlib.error("Error -3 while decompressing data: the gzip member at file offset %d breaks rule %d of "
-                                 "inflate_core.hpp" % (self.z_member, status))
-            if got:
-                lo = n0 + filled
-                if got >= 32768:
-                    self.z_window.copy_(data[lo + got - 32768:lo + got])
-                    self.z_wlen = 32768
-                else:
-                    both = torch.cat([self.z_window[:self.z_wlen], data[lo:lo + got]])[-32768:]
-                    self.z_wlen = both.numel()
-                    self.z_window[:self.z_wlen].copy_(both)
-                self.ratio = max(end_bit / 8.0 / got, 0.001)
-            filled += got
-            self.z_crc, self.z_isize = crc, (self.z_isize + got) & 0xffffffff
-            self.z_bit = 8 * byte + end_bit
-            if not final:
-                # the slab ended inside a block, or the next block's text does not fit: the next call says which, at
-                # the price of decoding the rest of the slab once more -- so a chunk that is half full ends here
-                if got < room and 2 * filled >= budget:
-                    break
-                if got < room and self.z_pos + self.z_n < self.size:
-                    self._stream_more(self.z_bit // 8, budget)
-                continue
-            trailer = (self.z_bit + 7) // 8
-            if trailer + 8 > self.z_n:
-                if not self._stream_more(self.z_bit // 8, budget):
-                    raise EOFError("Compressed file ended before the end-of-stream marker was reached")
-                trailer = (self.z_bit + 7) // 8
-                if trailer + 8 > self.z_n:
-                    raise EOFError("Compressed file ended before the end-of-stream marker was reached")
-            want_crc, want_size = struct.unpack("<II", bytes(buf[trailer:trailer + 8]))
-            if want_crc != self.z_crc:
-                raise gzip.BadGzipFile("CRC check failed for the gzip member at file offset %d (%#x != %#x)" % (self.z_member, want_crc, self.z_crc))
-            if want_size != self.z_isize:
-                raise gzip.BadGzipFile("Incorrect length of data produced by the gzip member at file offset %d " % self.z_member)
-            self.z_member, self.z_at = None, trailer + 8
-        nbytes = n0 + filled
-        data[nbytes:nbytes + 32].zero_()
-        return nbytes, self.z_done, data[:(nbytes + 15) // 16 * 16 + 16], None, None, None, 0, None
-
-    # ---- compressed input: one sequential decompressor, one chunk ahead
-    def _fill(self, k, carry):
-        view = memoryview(self.buf[k].numpy())
-        n0 = len(carry)
-        if n0:
-            view[:n0] = carry
-        room = self.buf[k].numel() - 32 - n0
-        want = max(self.chunk_bytes - n0, min(self.chunk_bytes // 4, room))
-        if want <= 0:
-            raise ValueError("FASTQ record of more than %d bytes" % self.buf[k].numel())
-        want, got = min(want, room), 0
-        while got < want:
-            n = self.stream.readinto(view[n0 + got:n0 + want])
-            if not n:
-                break
-            got += n
-        nbytes, final = n0 + got, got < want
-        host = self.buf[k]
-        unterminated = bool(final and nbytes and int(host[nbytes - 1]) not in (10, 13))
-        if unterminated:
-            host[nbytes] = 10                                 # tolerate a missing last newline (_seqio.pyx:240-243)
-            nbytes += 1
-        data = ready = None
-        if self.upload_stream is not None:
-            with torch.cuda.device(self.be.device), torch.cuda.stream(self.upload_stream):
-                data = torch.empty(((nbytes + 15) // 16 * 16 + 16,), dtype=torch.uint8, device=self.be.device)
-                data[:nbytes].copy_(host[:nbytes], non_blocking=True)
-                data[nbytes:].zero_()
-                ready = torch.cuda.Event()
-                ready.record()
-        return nbytes, final, unterminated, data, ready, host
-
-    def _index(self, data, nbytes, unterminated, host=None):
-        """The batch of the chunk's whole records in the file's format (its first chunk decides an unknown one)."""
-        if self.fmt == "bam":
-            return self._index_bam(data, nbytes)
-        if self.fmt is None:
-            head = host[:min(nbytes, 1 << 16)] if host is not None else data[:min(nbytes, 1 << 16)].cpu()
-            self.fmt = sniff_format(head.numpy().tobytes())
-            if self.fmt == "fasta" and self.byte_range:
-                raise NotImplementedError("a byte range of FASTA input is not provided")
-        cls = FastaBatch if self.fmt == "fasta" else FastqBatch
-        return cls.from_device(data, nbytes, self.final, self.be, unterminated=unterminated)
+    fmt = property(lambda self: self.decoder.fmt)
+    buf = property(lambda self: self.io.buf)                 # the staging buffers; [] after close
+    file = property(lambda self: self.io.file)
 
     def next_batch(self):
         """Upload and index the next chunk; returns the FastqBatch (FastaBatch) of its whole records."""
         t0 = time.perf_counter()
-        if self.bgzf:
-            data, nbytes, unterminated = self._next_device()
-            batch, self.consumed = self._index(data, nbytes, unterminated)
-            self.clock.add("upload_and_index", t0)
-            return batch
-        res = self.pending.result() if hasattr(self.pending, "result") else self.pending
-        self.nbytes, self.final, unterminated, data, ready, self.host = res
-        if self.stream is not None:
-            self.clock.add("wait_file_read", t0)
+        chunk = self.source.pending.result()                  # (raises what was met while it was put together)
+        self.clock.add("wait_file_read", t0)                  # the decompressor thread's chunk; every other is there already
         t0 = time.perf_counter()
-        host = self.host
-        nbytes = self.nbytes
-        if data is None:
-            data = self.be.empty(((nbytes + 15) // 16 * 16 + 16,), torch.uint8)
-            data[:nbytes].copy_(host[:nbytes], non_blocking=True)
-            data[nbytes:].zero_()
-        else:
-            with torch.cuda.device(self.be.device):
-                torch.cuda.current_stream().wait_event(ready)
-                data.record_stream(torch.cuda.current_stream())
-        batch, self.consumed = self._index(data, nbytes, unterminated, host)
+        chunk = self.source.take(chunk)
+        self.nbytes, self.final = chunk.nbytes, chunk.final
+        batch, self.consumed = self.decoder(chunk)
         self.clock.add("upload_and_index", t0)
         return batch
 
@@ -1161,43 +1296,14 @@ class ChunkedFastqReader(object):
         the rest is carried over and the next chunk is put together (plain files: its bytes are in the staging
         buffer already, its upload starts here).  Returns True when the file is exhausted and nothing is
         carried over."""
-        consumed = self.consumed if consumed is None else consumed
-        if self.bgzf:
-            n0 = self.nbytes - consumed
-            if self.final and not n0:
-                return True
-            self.carry_est = n0
-            self.pending = self._assemble_device((self.data, consumed, self.nbytes) if n0 else None)
-            return False
-        carry = bytes(self.host[consumed:self.nbytes].numpy().tobytes())
-        if self.final and not carry:
-            return True
-        if self.stream is not None:
-            self.k = 1 - self.k
-            self.pending = self.ahead.submit(self._fill, self.k, carry)
-        else:
-            self.pending = self._assemble(carry)
-        return False
+        source = self.source.advance(self.consumed if consumed is None else consumed)
+        self.source = source or self.source                   # (an ordinary member behind BGZF ones: another source goes on)
+        return source is None
 
     def close(self):
-        if self.bgzf:
-            for fut in self.reads:
-                fut.exception()                               # (a slab still being read owns its buffer)
-            for ev in self.uploaded:
-                if ev is not None:
-                    ev.synchronize()
-        elif self.stream is None:
-            for _, jobs, _, _ in self.reads:                  # reads still in flight own their buffers
-                for j in jobs:
-                    j.result()
-            for ev in self.uploaded:
-                if ev is not None:
-                    ev.synchronize()
-        self.readers.shutdown()
-        self.ahead.shutdown()
-        self.file.close()
-        _release(self.buf)
-        self.buf = []
+        if self.source is not None:
+            self.source.close()
+        self.io.close()
 
 
 def read_chunks(paths, chunk_bytes, backend=None, clock=None, byte_ranges=None, device_gunzip=False, interleaved=False,
@@ -1464,16 +1570,7 @@ class CompressedSink(object):
     outputs ``make_sink(..., device_gzip=True)`` compresses on the GPU instead (``DeviceGzipSink``)."""
 
     def __init__(self, path, clock=None):
-        name = str(path)
-        if name.endswith(".gz"):
-            import gzip
-            self.fh = gzip.open(name, "wb", compresslevel=6)
-        elif name.endswith(".bz2"):
-            import bz2
-            self.fh = bz2.open(name, "wb")
-        else:
-            import lzma
-            self.fh = lzma.open(name, "wb")
+        self.fh = open_by_extension(path)
         self.clock = clock or StageClock()
         self.writer = ThreadPoolExecutor(1)
         self.pending = []
@@ -1527,17 +1624,10 @@ class DeviceGzipSink(object):
 def open_by_extension(path):
     """A binary file object for writing; ``.gz`` / ``.bz2`` / ``.xz`` compress (the reference's xopen does so for EVERY
     output, the side files -- too-short, untrimmed, info, rest, wildcard -- included)."""
-    name = str(path)
-    if name.endswith(".gz"):
-        import gzip
-        return gzip.open(name, "wb", compresslevel=6)
-    if name.endswith(".bz2"):
-        import bz2
-        return bz2.open(name, "wb")
-    if name.endswith(".xz"):
-        import lzma
-        return lzma.open(name, "wb")
-    return open(name, "wb")
+    mod = _codec(path)
+    if mod is None:
+        return open(str(path), "wb")
+    return mod.open(str(path), "wb", **(dict(compresslevel=6) if mod.__name__ == "gzip" else {}))
 
 
 def make_sink(path, parts, capacity, backend=None, clock=None, keep=False, device_gzip=False):

@@ -100,7 +100,7 @@ def main():
         buf[:n] = torch.frombuffer(bytearray(raw[10:10 + n]), dtype=torch.uint8)
         stream = buf.to(be.device)
         window = be.empty((16,), torch.uint8)
-        spacing = 131072                                   # (ChunkedFastqReader.STREAM_SPACING)
+        spacing = 131072                                   # (ChunkedFastqReader.STREAM_SPACING: what fastq._GzipStreamSource spaces its starts by)
         work = be.empty((be.gunzip_stream_workspace(n, spacing, nbytes + 64),), torch.uint8)
         text.zero_()
         ms = []
