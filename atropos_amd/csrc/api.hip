@@ -63,7 +63,7 @@ locate_launcher locate_group_0(int), locate_group_1(int), locate_group_2(int), l
 
 static thread_local std::string g_err;
 
-int hip_fail(hipError_t e, const char *what) {             // shared with fastq_kernels.hip
+int hip_fail(hipError_t e, const char *what) {             // declared in launch_util.hpp for every kernel file
     g_err = std::string(what) + ": " + hipGetErrorString(e);
     return ATR_ERR_HIP;
 }

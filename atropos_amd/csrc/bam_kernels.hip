@@ -17,22 +17,14 @@
 
 #include "atropos_hip.h"
 #include "bam_core.hpp"
+
+#include "launch_util.hpp"
 #include "scan_kernels.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);             // api.hip
-
 namespace {
 
 constexpr int BAM_EMIT_LANES = 16;
-
-inline size_t bam_align(size_t x) { return (x + 255) & ~(size_t)255; }
-inline long long bam_blocks(long long n, long long per) { return (n + per - 1) / per; }
-inline int bam_launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ATR_OK : hip_fail(e, what);
-}
 
 // ------------------------------------------------------------------------- the walk
 __global__ __launch_bounds__(256) void bam_spec_kernel(const uint8_t *__restrict__ bytes, long long n, long long entry, int n_ref,
@@ -145,7 +137,23 @@ __global__ __launch_bounds__(256) void bam_emit_kernel(const uint8_t *__restrict
     if (error) bam_report(result, src, error);
 }
 
-inline unsigned bam_grid256(long long n) { return (unsigned)((n + 255) / 256); }
+// work layout of the walk: [BamTile x ntiles][uint2 x ntiles]
+struct WalkWork {
+    long long ntiles;
+    BamTile *tiles;
+    uint2 *placed;
+    size_t bytes;
+};
+
+WalkWork walk_work(void *work, long long n_bytes, long long tile_bytes) {
+    WalkWork w;
+    Workspace ws(work);
+    w.ntiles = blocks(n_bytes, tile_bytes);
+    w.tiles = ws.take<BamTile>((size_t)w.ntiles);
+    w.placed = ws.take<uint2>((size_t)w.ntiles);
+    w.bytes = ws.bytes();
+    return w;
+}
 
 }  // namespace
 }  // namespace atr
@@ -166,11 +174,9 @@ int atr_bam_header(const uint8_t *buf, int64_t n_bytes, int64_t *header_bytes, i
     return ATR_OK;
 }
 
-// work layout: [BamTile x ntiles][uint2 x ntiles]
 int64_t atr_bam_walk_workspace(int64_t n_bytes, int64_t tile_bytes) {
     if (n_bytes < 0 || tile_bytes < ATR_BAM_MIN_TILE || tile_bytes > ATR_BAM_MAX_TILE) return ATR_ERR_INVALID;
-    const long long ntiles = bam_blocks(n_bytes, tile_bytes);
-    return (int64_t)(bam_align((size_t)ntiles * sizeof(BamTile)) + bam_align((size_t)ntiles * sizeof(uint2)) + 256);
+    return (int64_t)walk_work(nullptr, n_bytes, tile_bytes).bytes;
 }
 
 int atr_bam_walk(const uint8_t *d_bam, int64_t n_bytes, int64_t entry, int32_t n_ref, int final, int64_t tile_bytes,
@@ -184,26 +190,24 @@ int atr_bam_walk(const uint8_t *d_bam, int64_t n_bytes, int64_t entry, int32_t n
         workspace_bytes < atr_bam_walk_workspace(n_bytes, tile_bytes))
         return ATR_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const long long ntiles = bam_blocks(n_bytes, tile_bytes);
-    BamTile *tiles = (BamTile *)d_workspace;
-    uint2 *placed = (uint2 *)((char *)d_workspace + bam_align((size_t)ntiles * sizeof(BamTile)));
+    const WalkWork w = walk_work(d_workspace, n_bytes, tile_bytes);
+    const long long ntiles = w.ntiles;
+    BamTile *tiles = w.tiles;
+    uint2 *placed = w.placed;
     if (ntiles)
-        hipLaunchKernelGGL(bam_spec_kernel, dim3((unsigned)bam_blocks(ntiles, 4)), dim3(256), 0, st, d_bam, (long long)n_bytes,
+        hipLaunchKernelGGL(bam_spec_kernel, dim3((unsigned)blocks(ntiles, 4)), dim3(256), 0, st, d_bam, (long long)n_bytes,
                            (long long)entry, (int)n_ref, (long long)tile_bytes, (long long)max_block, ntiles, tiles);
     hipLaunchKernelGGL(bam_resolve_kernel, dim3(1), dim3(64), 0, st, d_bam, (long long)n_bytes, (long long)entry, final,
                        (long long)tile_bytes, (long long)max_block, ntiles, (const BamTile *)tiles, placed, (long long *)d_result);
     if (ntiles)
-        hipLaunchKernelGGL(bam_starts_kernel, dim3(bam_grid256(ntiles)), dim3(256), 0, st, d_bam, (long long)n_bytes,
+        hipLaunchKernelGGL(bam_starts_kernel, dim3(grid256(ntiles)), dim3(256), 0, st, d_bam, (long long)n_bytes,
                            (long long)tile_bytes, ntiles, (const uint2 *)placed, (const long long *)d_result, d_starts,
                            (long long)starts_capacity);
-    return bam_launched("bam walk launch");
+    return launched("bam walk launch");
 }
 
-// work layout: [sizes u64 x n][sums u64 x blocks]
-size_t atr_bam_to_fastq_work_bytes(int64_t n) {
-    if (n < 0) return 0;
-    return bam_align((size_t)n * 8) + bam_align((size_t)scan_blocks(n) * 8 + 8) + 256;
-}
+// work layout: scan_work of 64-bit sizes, a spare word behind the sums
+size_t atr_bam_to_fastq_work_bytes(int64_t n) { return n < 0 ? 0 : scan_work_bytes<u64>(n, 1); }
 
 int atr_bam_to_fastq(const uint8_t *d_bam, int64_t n_bytes, const uint32_t *d_starts, int64_t n, int paired, int64_t *d_offsets,
                      int64_t *d_result, void *d_work, uint8_t *d_out, void *stream) {
@@ -216,19 +220,19 @@ int atr_bam_to_fastq(const uint8_t *d_bam, int64_t n_bytes, const uint32_t *d_st
     if (!d_out) {
         hipLaunchKernelGGL(bam_result_kernel, dim3(1), dim3(1), 0, st, (long long *)d_result, (long long *)d_offsets, used);
         if (used) {
-            u64 *sizes = (u64 *)d_work;
-            u64 *sums = (u64 *)((char *)d_work + bam_align((size_t)used * 8));
-            hipLaunchKernelGGL(bam_sizes_kernel, dim3(bam_grid256(used)), dim3(256), 0, st, d_bam, d_starts, used, paired, sizes,
+            Workspace ws(d_work);
+            const ScanWork<u64> w = scan_work<u64>(ws, used, 1);
+            hipLaunchKernelGGL(bam_sizes_kernel, dim3(grid256(used)), dim3(256), 0, st, d_bam, d_starts, used, paired, w.sizes,
                                (long long *)d_result);
-            device_scan(sizes, used, (u64 *)d_offsets, sums, st);
+            device_scan(w.sizes, used, (u64 *)d_offsets, w.sums, (u64 *)d_offsets + used, st);
             hipLaunchKernelGGL(bam_total_kernel, dim3(1), dim3(1), 0, st, (const long long *)d_offsets, used, (long long *)d_result);
         }
-        return bam_launched("bam decode sizes launch");
+        return launched("bam decode sizes launch");
     }
     if (used)
-        hipLaunchKernelGGL(bam_emit_kernel, dim3((unsigned)bam_blocks(used * BAM_EMIT_LANES, 256)), dim3(256), 0, st, d_bam,
+        hipLaunchKernelGGL(bam_emit_kernel, dim3((unsigned)blocks(used * BAM_EMIT_LANES, 256)), dim3(256), 0, st, d_bam,
                            d_starts, used, paired, (const long long *)d_offsets, d_out, (long long *)d_result);
-    return bam_launched("bam decode launch");
+    return launched("bam decode launch");
 }
 
 }  // extern "C"

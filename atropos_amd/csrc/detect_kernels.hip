@@ -24,12 +24,11 @@
 #include <new>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "detect_core.hpp"
 #include "fastq_core.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);             // api.hip
 
 typedef unsigned long long u64;
 
@@ -242,11 +241,6 @@ __global__ __launch_bounds__(256) void det_match_kernel(DetDev D, const uint8_t 
 
 using namespace atr;
 
-static inline int det_launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ATR_OK : hip_fail(e, what);
-}
-
 static inline unsigned det_grid(long long waves) {
     return (unsigned)std::max<long long>(1, std::min<long long>((waves + 3) / 4, 4096));
 }
@@ -320,7 +314,7 @@ int atr_detect_filter_batch(const void *handle, const uint8_t *d_bytes, const at
     if (!d_bytes || !d_records || !d_kept || !d_hashes || !d_counters) return ATR_ERR_INVALID;
     hipLaunchKernelGGL(det_filter_kernel, dim3(det_grid(n)), dim3(256), 0, (hipStream_t)stream, h->D, d_bytes,
                        (const FastqRecord *)d_records, (long long)n, d_kept, (long long *)d_hashes, (u64 *)d_counters);
-    return det_launched("atr_detect_filter_batch launch");
+    return launched("atr_detect_filter_batch launch");
 }
 
 int atr_detect_mark_batch(const void *handle, const uint8_t *d_bytes, const atr_fastq_record *d_records,
@@ -332,7 +326,7 @@ int atr_detect_mark_batch(const void *handle, const uint8_t *d_bytes, const atr_
     hipLaunchKernelGGL(det_mark_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_bytes,
                        (const FastqRecord *)d_records, d_kept, (const long long *)d_order, (const long long *)d_head,
                        (long long)m, d_rep, (u64 *)d_counters);
-    return det_launched("atr_detect_mark_batch launch");
+    return launched("atr_detect_mark_batch launch");
 }
 
 int atr_detect_batch(const void *handle, const uint8_t *d_bytes, const atr_fastq_record *d_records, const int32_t *d_kept,
@@ -344,7 +338,7 @@ int atr_detect_batch(const void *handle, const uint8_t *d_bytes, const atr_fastq
     hipLaunchKernelGGL(det_match_kernel, dim3(det_grid(m)), dim3(256), h->lds, (hipStream_t)stream, h->D, d_bytes,
                        (const FastqRecord *)d_records, d_kept, (const long long *)d_order, d_rep, (long long)m,
                        (u64 *)d_counters);
-    return det_launched("atr_detect_batch launch");
+    return launched("atr_detect_batch launch");
 }
 
 int atr_detect_read(const void *handle, const void *d_counters, uint64_t *out, void *stream) {

@@ -17,22 +17,14 @@
 
 #include "atropos_hip.h"
 #include "fasta_core.hpp"
+
+#include "launch_util.hpp"
 #include "scan_kernels.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);             // api.hip
-
 namespace {
 
 constexpr int FA_NL = 256, FA_NL_BYTES = FA_NL * 16;      // line index: threads per block, bytes per block
-
-inline size_t fa_align(size_t x) { return (x + 255) & ~(size_t)255; }
-inline long long fa_blocks(long long n, long long per) { return (n + per - 1) / per; }
-inline int fa_launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ATR_OK : hip_fail(e, what);
-}
 
 // ------------------------------------------------------------------------- line index
 // bit i set <=> byte off + i ends a line (is_line_end of fastq_core.hpp; the byte behind the text counts as 0)
@@ -211,27 +203,24 @@ struct FaWork {
     size_t bytes;
 };
 
-FaWork fa_work(void *work, long long nbytes, long long nlines) {
+FaWork fa_work(const void *work, long long nbytes, long long nlines) {
     FaWork w;
-    char *p = (char *)work;
-    size_t o = 0;
-    const long long nblk = fa_blocks(nbytes, FA_NL_BYTES);
-    w.counts = (u64 *)(p + o); o += fa_align((size_t)nblk * 8);
-    w.base = (u64 *)(p + o); o += fa_align((size_t)(nblk + 1) * 8);
-    w.csums = (u64 *)(p + o); o += fa_align((size_t)fa_blocks(nblk, SCAN_BLOCK) * 8 + 8);
-    w.cls = (uint8_t *)(p + o); o += fa_align((size_t)nlines);
-    w.at = (uint32_t *)(p + o); o += fa_align((size_t)nlines * 4);
-    w.len = (uint32_t *)(p + o); o += fa_align((size_t)nlines * 4);
-    w.head_line = (uint32_t *)(p + o); o += fa_align((size_t)nlines * 4);
-    w.value = (u64 *)(p + o); o += fa_align((size_t)nlines * 8);
-    w.pre = (u64 *)(p + o); o += fa_align((size_t)(nlines + 1) * 8);
-    w.tail_pre = (u64 *)(p + o); o += fa_align((size_t)(nlines + 1) * 8);
-    w.sums = (u64 *)(p + o); o += fa_align((size_t)fa_blocks(nlines, SCAN_BLOCK) * 8 + 8);
-    w.bytes = o + 256;
+    Workspace ws(work);
+    const long long nblk = blocks(nbytes, FA_NL_BYTES);
+    w.counts = ws.take<u64>((size_t)nblk);
+    w.base = ws.take<u64>((size_t)nblk + 1);
+    w.csums = ws.take<u64>((size_t)scan_blocks(nblk) + 1);
+    w.cls = ws.take<uint8_t>((size_t)nlines);
+    w.at = ws.take<uint32_t>((size_t)nlines);
+    w.len = ws.take<uint32_t>((size_t)nlines);
+    w.head_line = ws.take<uint32_t>((size_t)nlines);
+    w.value = ws.take<u64>((size_t)nlines);
+    w.pre = ws.take<u64>((size_t)nlines + 1);
+    w.tail_pre = ws.take<u64>((size_t)nlines + 1);
+    w.sums = ws.take<u64>((size_t)scan_blocks(nlines) + 1);
+    w.bytes = ws.bytes();
     return w;
 }
-
-inline unsigned fa_grid256(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 }  // namespace atr
@@ -249,32 +238,32 @@ int atr_fasta_scan(const uint8_t *d_bytes, int64_t nbytes, uint32_t *d_line_ends
                    int64_t *d_info, void *stream) {
     if (nbytes < 0 || nbytes >= (int64_t)0xFFFFFFF0ll || nlines < 0 || nlines > nbytes || !d_info) return ATR_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(scan_set_kernel, dim3(1), dim3(1), 0, st, (long long *)d_info + 2, (long long)LLONG_MAX);
+    hipLaunchKernelGGL(set_i64_kernel, dim3(1), dim3(1), 0, st, (long long *)d_info + 2, (long long)LLONG_MAX);
     if (nlines == 0) {
         hipError_t e = hipMemsetAsync(d_info, 0, 16, st);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
-        return fa_launched("fasta scan launch");
+        return launched("fasta scan launch");
     }
     if (!d_bytes || !d_work || !d_line_ends || ((uintptr_t)d_bytes & 15)) return ATR_ERR_INVALID;
     const FaWork w = fa_work(d_work, nbytes, nlines);
-    const long long nblk = fa_blocks(nbytes, FA_NL_BYTES);
+    const long long nblk = blocks(nbytes, FA_NL_BYTES);
     // (the blocks' line counts: atr_fastq_count_lines keeps its own to itself)
     hipLaunchKernelGGL(fa_count_kernel, dim3((unsigned)nblk), dim3(FA_NL), 0, st, d_bytes, (long long)nbytes, w.counts);
-    device_scan(w.counts, nblk, w.base, w.csums, st);
+    device_scan(w.counts, nblk, w.base, w.csums, w.base + nblk, st);
     hipLaunchKernelGGL(fa_line_ends_kernel, dim3((unsigned)nblk), dim3(FA_NL), 0, st, d_bytes, (long long)nbytes,
                        (const u64 *)w.base, (long long)nlines, d_line_ends);
-    hipLaunchKernelGGL(fa_classify_kernel, dim3(fa_grid256(nlines)), dim3(256), 0, st, d_bytes, (const uint32_t *)d_line_ends,
+    hipLaunchKernelGGL(fa_classify_kernel, dim3(grid256(nlines)), dim3(256), 0, st, d_bytes, (const uint32_t *)d_line_ends,
                        (long long)nlines, w.cls, w.at, w.len, w.value);
-    device_scan(w.value, nlines, w.pre, w.sums, st);
-    hipLaunchKernelGGL(fa_heads_kernel, dim3(fa_grid256(nlines)), dim3(256), 0, st, (const uint8_t *)w.cls, (const u64 *)w.pre,
+    device_scan(w.value, nlines, w.pre, w.sums, w.pre + nlines, st);
+    hipLaunchKernelGGL(fa_heads_kernel, dim3(grid256(nlines)), dim3(256), 0, st, (const uint8_t *)w.cls, (const u64 *)w.pre,
                        (long long)nlines, w.head_line, (u64 *)d_info + 2);
-    hipLaunchKernelGGL(fa_gather_sizes_kernel, dim3(fa_grid256(nlines)), dim3(256), 0, st, (const uint32_t *)d_line_ends,
+    hipLaunchKernelGGL(fa_gather_sizes_kernel, dim3(grid256(nlines)), dim3(256), 0, st, (const uint32_t *)d_line_ends,
                        (const uint8_t *)w.cls, (const uint32_t *)w.at, (const uint32_t *)w.len, (const u64 *)w.pre,
                        (const uint32_t *)w.head_line, (long long)nlines, w.value);
-    device_scan(w.value, nlines, w.tail_pre, w.sums, st);
+    device_scan(w.value, nlines, w.tail_pre, w.sums, w.tail_pre + nlines, st);
     hipLaunchKernelGGL(fa_info_kernel, dim3(1), dim3(1), 0, st, (const u64 *)w.pre, (const u64 *)w.tail_pre, (long long)nlines,
                        (long long *)d_info);
-    return fa_launched("fasta scan launch");
+    return launched("fasta scan launch");
 }
 
 int atr_fasta_index(uint8_t *d_bytes, int64_t nbytes, const uint32_t *d_line_ends, int64_t nlines, const void *d_work,
@@ -286,24 +275,21 @@ int atr_fasta_index(uint8_t *d_bytes, int64_t nbytes, const uint32_t *d_line_end
     if (nrec == 0) return ATR_OK;
     if (!d_bytes || !d_work || !d_line_ends || !d_records || !d_record_ends || ((uintptr_t)d_bytes & 15)) return ATR_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const FaWork w = fa_work(const_cast<void *>(d_work), nbytes, nlines);
-    hipLaunchKernelGGL(fa_records_kernel, dim3(fa_grid256(nrec)), dim3(256), 0, st, d_line_ends, (const uint8_t *)w.cls,
+    const FaWork w = fa_work(d_work, nbytes, nlines);
+    hipLaunchKernelGGL(fa_records_kernel, dim3(grid256(nrec)), dim3(256), 0, st, d_line_ends, (const uint8_t *)w.cls,
                        (const uint32_t *)w.at, (const uint32_t *)w.len, (const u64 *)w.pre, (const uint32_t *)w.head_line,
                        (long long)nlines, (long long)nrec, (const u64 *)w.tail_pre, (uint32_t)tail_off, (FastqRecord *)d_records,
                        d_record_ends);
     if (tail_bytes > 0)
-        hipLaunchKernelGGL(fa_gather_kernel, dim3((unsigned)fa_blocks(nlines, 4)), dim3(256), 0, st, d_bytes, d_line_ends,
+        hipLaunchKernelGGL(fa_gather_kernel, dim3((unsigned)blocks(nlines, 4)), dim3(256), 0, st, d_bytes, d_line_ends,
                            (const uint8_t *)w.cls, (const uint32_t *)w.at, (const uint32_t *)w.len, (const u64 *)w.pre,
                            (const uint32_t *)w.head_line, (long long)nlines, (long long)nrec, (const u64 *)w.tail_pre,
                            (uint32_t)tail_off, (uint32_t)tail_bytes);
-    return fa_launched("fasta index launch");
+    return launched("fasta index launch");
 }
 
-// work layout: [sizes u64 x n][sums u64 x blocks]
-size_t atr_fasta_emit_work_bytes(int64_t n) {
-    if (n < 0) return 0;
-    return fa_align((size_t)n * 8) + fa_align((size_t)fa_blocks(n, SCAN_BLOCK) * 8 + 8) + 256;
-}
+// work layout: scan_work of 64-bit sizes, a spare word behind the sums
+size_t atr_fasta_emit_work_bytes(int64_t n) { return n < 0 ? 0 : scan_work_bytes<u64>(n, 1); }
 
 int atr_fasta_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, const int32_t *d_begin,
                    const int32_t *d_end, const int32_t *d_unmasked_begin, const int32_t *d_unmasked_end,
@@ -313,22 +299,22 @@ int atr_fasta_emit(const uint8_t *d_bytes, const atr_fastq_record *d_records, co
     if (n < 0 || !d_offsets || ((d_unmasked_begin == nullptr) != (d_unmasked_end == nullptr))) return ATR_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        if (!d_out) hipLaunchKernelGGL(scan_set_kernel, dim3(1), dim3(1), 0, st, (long long *)d_offsets, 0ll);
-        return fa_launched("fasta emit launch");
+        if (!d_out) hipLaunchKernelGGL(set_i64_kernel, dim3(1), dim3(1), 0, st, (long long *)d_offsets, 0ll);
+        return launched("fasta emit launch");
     }
     if (!d_bytes || !d_records || !d_begin || !d_end || !d_work) return ATR_ERR_INVALID;
     if (!d_out) {
-        u64 *sizes = (u64 *)d_work;
-        u64 *sums = (u64 *)((char *)d_work + fa_align((size_t)n * 8));
-        hipLaunchKernelGGL(fa_emit_sizes_kernel, dim3(fa_grid256(n)), dim3(256), 0, st, (const FastqRecord *)d_records, d_begin,
-                           d_end, d_dest, dest, (long long)n, sizes);
-        device_scan(sizes, n, (u64 *)d_offsets, sums, st);
-        return fa_launched("fasta emit sizes launch");
+        Workspace ws(d_work);
+        const ScanWork<u64> w = scan_work<u64>(ws, n, 1);
+        hipLaunchKernelGGL(fa_emit_sizes_kernel, dim3(grid256(n)), dim3(256), 0, st, (const FastqRecord *)d_records, d_begin,
+                           d_end, d_dest, dest, (long long)n, w.sizes);
+        device_scan(w.sizes, n, (u64 *)d_offsets, w.sums, (u64 *)d_offsets + n, st);
+        return launched("fasta emit sizes launch");
     }
-    hipLaunchKernelGGL(fa_emit_kernel, dim3((unsigned)fa_blocks(n * FA_EMIT_LANES, 256)), dim3(256), 0, st, d_bytes,
+    hipLaunchKernelGGL(fa_emit_kernel, dim3((unsigned)blocks(n * FA_EMIT_LANES, 256)), dim3(256), 0, st, d_bytes,
                        (const FastqRecord *)d_records, d_begin, d_end, d_unmasked_begin, d_unmasked_end, d_dest, dest,
                        (long long)n, (const long long *)d_offsets, d_out);
-    return fa_launched("fasta emit launch");
+    return launched("fasta emit launch");
 }
 
 }  // extern "C"

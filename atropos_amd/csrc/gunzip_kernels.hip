@@ -11,11 +11,10 @@
 #include <hip/hip_runtime.h>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "inflate_core.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);             // api.hip
 
 __global__ __launch_bounds__(INF_NT) void gunzip_kernel(const uint8_t *__restrict__ stream, long long n_stream,
                                                         const long long *__restrict__ member_at, const long long *__restrict__ text_at,

@@ -12,11 +12,10 @@
 #include <hip/hip_runtime.h>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "inflate_stream_core.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);             // api.hip
 
 __global__ __launch_bounds__(INF_NT) void ist_find_kernel(IstCall k) {
     __shared__ InfTables lds;

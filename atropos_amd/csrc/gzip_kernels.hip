@@ -13,10 +13,9 @@
 
 #include "atropos_hip.h"
 #include "deflate_core.hpp"
+#include "launch_util.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);             // api.hip
 
 __global__ __launch_bounds__(GZ_NT) void gz_blocks_kernel(const uint8_t *__restrict__ text, long long n, long long nblocks,
                                                           uint8_t *slots, uint32_t *sizes, uint32_t *match) {
@@ -66,11 +65,6 @@ __global__ __launch_bounds__(256) void gz_gather_kernel(const uint8_t *__restric
     for (uint32_t i = threadIdx.x; i < size; i += 256) dst[i] = src[i];
 }
 
-static inline int gz_launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ATR_OK : hip_fail(e, what);
-}
-
 }  // namespace atr
 
 using namespace atr;
@@ -107,14 +101,14 @@ int atr_gzip_blocks(const uint8_t *d_text, int64_t n_bytes, uint8_t *d_out, int6
     uint32_t *match = (uint32_t *)(work + gz_work_match_at(n_bytes));
     hipLaunchKernelGGL(gz_blocks_kernel, dim3((unsigned)gz_grid(n_bytes)), dim3(GZ_NT), 0, s, d_text, (long long)n_bytes,
                        nblocks, work, sizes, match);
-    int rc = gz_launched("atr_gzip_blocks launch");
+    int rc = launched("atr_gzip_blocks launch");
     if (rc) return rc;
     hipLaunchKernelGGL(gz_scan_kernel, dim3(1), dim3(1024), 0, s, sizes, nblocks, offsets, (long long *)d_member_offsets,
                        (long long *)d_total);
-    rc = gz_launched("atr_gzip_blocks scan launch");
+    rc = launched("atr_gzip_blocks scan launch");
     if (rc) return rc;
     hipLaunchKernelGGL(gz_gather_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, work, sizes, offsets, d_out);
-    return gz_launched("atr_gzip_blocks gather launch");
+    return launched("atr_gzip_blocks gather launch");
 }
 
 }  // extern "C"

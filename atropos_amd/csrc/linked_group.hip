@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "linked_host.hpp"
 #include "linked_blob.hpp"
 #include "pack_fast.hpp"
@@ -31,7 +32,6 @@
 
 namespace atr {
 
-int hip_fail(hipError_t e, const char *what);
 bool piece_applies(const atr_aligner *a, int max_len, FilterParams *fp_out, PieceParams *pp_out);      // piece_kernels.hip
 int piece_ragged_len(int max_len);
 int launch_planes_prepass(const atr_aligner *a, const uint4 *planes, const int32_t *lens, long long nreads, int max_len,

@@ -16,6 +16,7 @@
 #include <string>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "linked_host.hpp"
 #include "locate_fast.hpp"
 #include "wave_sweep.hpp"
@@ -26,7 +27,6 @@ namespace atr {
 void launch_fast_scan(FastWork wk, hipStream_t st);
 int launch_fast_dp(const atr_aligner *a, const uint4 *packed, const int32_t *lens, long long nreads, int nchunks,
                    int max_len, uint4 *out, FastWork wk, const LinkedArgs *la, int idx, int count, hipStream_t st, bool planes, bool one_stream);
-int hip_fail(hipError_t e, const char *what);
 
 
 

@@ -17,13 +17,13 @@
 #include <algorithm>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "locate_fast.hpp"
 #include "side_stream.hpp"
 #include "pairs_fast_core.hpp"
 
 namespace atr {
 
-int hip_fail(hipError_t e, const char *what);             // api.hip
 __global__ void scan_bins_kernel(FastWork wk);            // filter_kernels.hip
 __global__ void scan_total_kernel(FastWork wk);
 

@@ -8,13 +8,12 @@
 #include <cstring>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "pairs_core.hpp"
 #include "pairs_fast_core.hpp"
 #include "wave_core.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);             // api.hip
 
 // The pairs the fast pipeline (pairs_fast.hip) hands to the full sweep arrive as a slot range of its task list:
 // order[range[0] .. range[1]) (both on the device; .x of a task = the pair).  order == nullptr: all pairs in turn.

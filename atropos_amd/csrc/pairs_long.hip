@@ -3,11 +3,10 @@
 #include <hip/hip_runtime.h>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "pairs_long_core.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);
 
 template <bool AND_MODE>
 __global__ __launch_bounds__(64) void pairs_long_kernel(const PairLongParams p, const uint4 *__restrict__ ref_packed,

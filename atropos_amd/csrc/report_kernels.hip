@@ -19,12 +19,11 @@
 #include <new>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "fastq_core.hpp"
 #include "report_core.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);             // api.hip
 
 typedef unsigned long long u64;
 
@@ -144,11 +143,6 @@ __global__ __launch_bounds__(256) void rep_outputs_kernel(const FastqRecord *__r
 
 using namespace atr;
 
-static inline int rep_launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ATR_OK : hip_fail(e, what);
-}
-
 static inline unsigned rep_grid(long long n) {
     return (unsigned)std::max<long long>(1, std::min<long long>((n + 1023) / 1024, 1024));
 }
@@ -185,7 +179,7 @@ int atr_report_intervals(const void *report, const atr_fastq_record *d_records, 
     hipLaunchKernelGGL(rep_intervals_kernel, dim3(rep_grid(n)), dim3(256), 0, (hipStream_t)stream,
                        (const FastqRecord *)d_records, d_begin0, d_end0, d_begin1, d_end1, (long long)n, mode, front, back,
                        (u64 *)d_counters + REP_TRIM + slot);
-    return rep_launched("atr_report_intervals launch");
+    return launched("atr_report_intervals launch");
 }
 
 int atr_report_adapters(const void *report, const uint8_t *d_bytes, const atr_fastq_record *d_records, const uint8_t *d_took,
@@ -209,7 +203,7 @@ int atr_report_adapters(const void *report, const uint8_t *d_bytes, const atr_fa
                        in_lds ? longest : -1, d_bytes, (const FastqRecord *)d_records, d_took, d_best,
                        (const long long *)d_which, d_front, default_front, d_begin, d_end, (long long)n, (unsigned)weight,
                        (u64 *)d_counters);
-    return rep_launched("atr_report_adapters launch");
+    return launched("atr_report_adapters launch");
 }
 
 int atr_report_outputs(const void *report, const atr_fastq_record *d_records, const int32_t *d_begin, const int32_t *d_end,
@@ -219,7 +213,7 @@ int atr_report_outputs(const void *report, const atr_fastq_record *d_records, co
     if (!d_records || !d_begin || !d_end || !d_matched || !d_dest || !d_counters) return ATR_ERR_INVALID;
     hipLaunchKernelGGL(rep_outputs_kernel, dim3(rep_grid(n)), dim3(256), 0, (hipStream_t)stream,
                        (const FastqRecord *)d_records, d_begin, d_end, d_matched, d_dest, (long long)n, (u64 *)d_counters);
-    return rep_launched("atr_report_outputs launch");
+    return launched("atr_report_outputs launch");
 }
 
 int atr_report_read(const void *report, const void *d_counters, int64_t *out, void *stream) {

@@ -1,10 +1,14 @@
-// scan_kernels.hpp -- the exclusive prefix sum over 64-bit values that the FASTA index (fasta_kernels.hip) and the BAM
-// decode (bam_kernels.hip) lay their outputs out with: a block scan, the blocks' totals scanned by one block, the add.
-// No atomics: equal input gives equal sums.  Included by the kernel files; every one gets kernels of its own.
+// scan_kernels.hpp -- the exclusive prefix sum that every text kernel file lays its outputs out with (the line index
+// and the formatters of fastq_kernels.hip, fastq_emit_kernels.hip and pairtext_kernels.hip, the FASTA index, the BAM
+// decode): a block scan, the blocks' totals scanned by one block, the add.  The input is 32- or 64-bit words, the
+// sums are 64-bit.  No atomics: equal input gives equal sums, input order is kept.  Included by the kernel files;
+// every one gets kernels of its own.
 #ifndef ATR_SCAN_KERNELS_HPP
 #define ATR_SCAN_KERNELS_HPP
 
 #include <hip/hip_runtime.h>
+
+#include "launch_util.hpp"
 
 namespace atr {
 namespace {
@@ -42,20 +46,20 @@ __device__ __forceinline__ u64 scan_block(u64 v, u64 *s_part, u64 *total) {
 }
 
 // out[i] = exclusive prefix of v inside its block, sums[b] = the block's total
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_local_kernel(const u64 *__restrict__ v, long long n, u64 *__restrict__ out,
+template <typename V>
+__global__ __launch_bounds__(SCAN_BLOCK) void scan_local_kernel(const V *__restrict__ v, long long n, u64 *__restrict__ out,
                                                                 u64 *__restrict__ sums) {
     __shared__ u64 s_part[SCAN_BLOCK / 64];
     const long long i = (long long)blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    const u64 x = i < n ? v[i] : 0ull;
+    const u64 x = i < n ? (u64)v[i] : 0ull;
     u64 total;
     const u64 inc = scan_block<SCAN_BLOCK>(x, s_part, &total);
     if (i < n) out[i] = inc - x;
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
-// exclusive prefix of the nb block totals in place (one block, a run per thread); out[n] = the grand total
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_sums_kernel(u64 *__restrict__ sums, long long nb, u64 *__restrict__ out,
-                                                               long long n) {
+// exclusive prefix of the nb block totals in place (one block, a run per thread); *total_out = the grand total
+__global__ __launch_bounds__(SCAN_BLOCK) void scan_sums_kernel(u64 *__restrict__ sums, long long nb, u64 *__restrict__ total_out) {
     __shared__ u64 s_part[SCAN_BLOCK / 64];
     const long long per = (nb + SCAN_BLOCK - 1) / SCAN_BLOCK;
     const long long lo = min(nb, per * (long long)threadIdx.x), hi = min(nb, lo + per);
@@ -65,7 +69,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_sums_kernel(u64 *__restrict__
     const u64 inc = scan_block<SCAN_BLOCK>(mine, s_part, &total);
     u64 run = inc - mine;
     for (long long i = lo; i < hi; ++i) { const u64 t = sums[i]; sums[i] = run; run += t; }
-    if (threadIdx.x == 0) out[n] = total;
+    if (threadIdx.x == 0 && total_out) *total_out = total;
 }
 
 __global__ __launch_bounds__(SCAN_BLOCK) void scan_add_kernel(u64 *__restrict__ out, long long n, const u64 *__restrict__ sums) {
@@ -73,18 +77,43 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_add_kernel(u64 *__restrict__ 
     if (i < n) out[i] += sums[blockIdx.x];
 }
 
-__global__ void scan_set_kernel(long long *p, long long v) { *p = v; }
+__global__ void set_i64_kernel(long long *p, long long v) { *p = v; }
 
-// out[0 .. n] = exclusive prefix sums of v[0 .. n), out[n] the total; sums: scan_blocks(n) words
-void device_scan(const u64 *v, long long n, u64 *out, u64 *sums, hipStream_t st) {
+// out[0 .. n) = exclusive prefix sums of v[0 .. n); *total, where one is given, = the sum of all of v (0 for n == 0,
+// which writes nothing else).  `total` may be out + n, and need not be: an array of exactly n words stays inside
+// its bounds.  sums: scan_blocks(n) words.
+template <typename V>
+void device_scan(const V *v, long long n, u64 *out, u64 *sums, u64 *total, hipStream_t st) {
     if (n == 0) {
-        hipLaunchKernelGGL(scan_set_kernel, dim3(1), dim3(1), 0, st, (long long *)out, 0ll);
+        if (total) hipLaunchKernelGGL(set_i64_kernel, dim3(1), dim3(1), 0, st, (long long *)total, 0ll);
         return;
     }
     const long long nb = scan_blocks(n);
-    hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, v, n, out, sums);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, sums, nb, out, n);
+    hipLaunchKernelGGL(scan_local_kernel<V>, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, v, n, out, sums);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, sums, nb, total);
     hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, out, n, (const u64 *)sums);
+}
+
+// the workspace of one "sizes -> offsets" step: [sizes V x n][sums u64 x (scan_blocks(n) + spare)]
+template <typename V>
+struct ScanWork {
+    V *sizes;
+    u64 *sums;
+};
+
+template <typename V>
+ScanWork<V> scan_work(Workspace &ws, long long n, int spare = 0) {
+    ScanWork<V> w;
+    w.sizes = ws.take<V>((size_t)n);
+    w.sums = ws.take<u64>((size_t)scan_blocks(n) + spare);
+    return w;
+}
+
+template <typename V>
+size_t scan_work_bytes(long long n, int spare = 0) {
+    Workspace ws(nullptr);
+    scan_work<V>(ws, n, spare);
+    return ws.bytes();
 }
 
 }  // namespace

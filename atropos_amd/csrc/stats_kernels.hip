@@ -23,12 +23,11 @@
 #include <algorithm>
 
 #include "atropos_hip.h"
+#include "launch_util.hpp"
 #include "fastq_core.hpp"
 #include "stats_core.hpp"
 
 namespace atr {
-
-int hip_fail(hipError_t e, const char *what);             // api.hip
 
 constexpr int ST_WIN = 64;             // positions per window of the position kernel (one per lane)
 constexpr int ST_QSYM = 94;            // quality bytes '!' .. '~' kept in LDS
@@ -291,11 +290,6 @@ __global__ __launch_bounds__(256) void stats_merge_kernel(u64 *__restrict__ dst,
 
 using namespace atr;
 
-static inline int st_launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ATR_OK : hip_fail(e, what);
-}
-
 static inline int st_check_len(int max_len) {
     if (max_len < 1) return ATR_ERR_INVALID;
     if (max_len > ATR_MAX_LONG_READ_LEN) return ATR_ERR_UNSUPPORTED;
@@ -342,7 +336,7 @@ int atr_read_stats_batch(void *d_stats, int max_len, int longest, int quality_ba
         const long long gx = std::max<long long>(1, std::min<long long>(blocks, std::max(64, 3072 / nwin)));
         hipLaunchKernelGGL(stats_position_kernel, dim3((unsigned)gx, (unsigned)nwin), dim3(256), 0, st, A);
     }
-    return st_launched("atr_read_stats_batch launch");
+    return launched("atr_read_stats_batch launch");
 }
 
 int atr_read_stats_merge(void *d_dst, int dst_max_len, const void *d_src, int src_max_len, int64_t index_offset,
@@ -354,7 +348,7 @@ int atr_read_stats_merge(void *d_dst, int dst_max_len, const void *d_src, int sr
     const long long total = st_words(src_max_len);
     hipLaunchKernelGGL(stats_merge_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0,
                        (hipStream_t)stream, (u64 *)d_dst, dst_max_len, (const u64 *)d_src, src_max_len, (u64)index_offset);
-    return st_launched("atr_read_stats_merge launch");
+    return launched("atr_read_stats_merge launch");
 }
 
 }  // extern "C"

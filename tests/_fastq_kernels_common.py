@@ -1,5 +1,5 @@
 """Shared by test_fastq_kernels_host.py (the CPU twin, tests/emu/emu_fastq.cpp) and test_gpu_fastq_kernels.py (the
-kernels of atropos_amd/csrc/fastq_kernels.hip): a plain Python model of the FASTQ text kernels -- line index, record
+kernels of atropos_amd/csrc/fastq_kernels.hip and fastq_emit_kernels.hip): a plain Python model of the FASTQ text kernels -- line index, record
 descriptors, formatter, interval modifiers, filters, the pack from records -- the case builders that put the inputs
 on the kernels' edges, and the ``check_*`` functions that call the kernels at the C ABI with those inputs.
 
@@ -17,7 +17,7 @@ ERR_AT, ERR_PLUS, ERR_NAME2, ERR_LENGTH = 1, 2, 3, 4            # ATR_FASTQ_ERR_
 LF, CRLF, CR = b"\n", b"\r\n", b"\r"
 GUARD = 64                                                      # bytes of 0xEE in front of and behind every formatter output
 # atr_fastq_emit's staged instantiations: record_bytes_hint -> (records per tile, bytes per stage).  The stage sizes
-# are EMIT_STAGE = 13 * 1024 of fastq_kernels.hip: <32> whole, <8> EMIT_STAGE / 4, <16> EMIT_STAGE / 2, <16> whole.
+# are EMIT_STAGE = 13 * 1024 of fastq_device.hpp: <32> whole, <8> EMIT_STAGE / 4, <16> EMIT_STAGE / 2, <16> whole.
 EMIT_VARIANTS = ((0, 32, 13312), (300, 8, 3328), (390, 16, 6656), (500, 16, 13312))
 NAME_LETTERS = np.frombuffer(b"abcXYZ019:/_-.# @+", np.uint8)
 SEQ_LETTERS = np.frombuffer(b"ACGT" * 6 + b"Nacgtn", np.uint8)
@@ -416,6 +416,48 @@ def check_emit_stage_limit(be):
 
 
 # ---------------------------------------------------------------------------------------------- index: cases
+# n records through the shared "sizes -> offsets -> total" step (device_scan of scan_kernels.hpp): one block, the block
+# edge, two and three blocks, and 1026 blocks -- there every thread of scan_sums_kernel owns a run of two block totals,
+# threads 0 .. 512 are busy and the rest are empty.
+OFFSET_COUNTS = (0, 1, 1023, 1024, 1025, 2048, 2049, 1048576 + 1025)
+
+
+def offsets_case(n, seed=41):
+    """(text, record texts, dest) of n records with hexadecimal names and 1 to 3 bases: record sizes that are no
+    multiple of anything, and a dest mask that keeps about half of the records."""
+    rng = np.random.default_rng(seed + n)
+    lens = rng.integers(1, 4, size=n).tolist()
+    bases = SEQ_LETTERS[rng.integers(0, len(SEQ_LETTERS), size=n + 3)].tobytes()
+    quals = rng.integers(33, 74, size=n + 3).astype(np.uint8).tobytes()
+    pieces = [b"@%x\n%s\n+\n%s\n" % (r, bases[r:r + k], quals[r:r + k]) for r, k in enumerate(lens)]
+    return b"".join(pieces), pieces, rng.integers(0, 2, size=n).astype(np.uint8)
+
+
+def check_emit_offsets(be):
+    """atr_fastq_emit over OFFSET_COUNTS records, indexed on the device, half of them kept by ``dest``: the text byte
+    for byte against a ``bytes.join`` over the kept records, every offset and the total against the running sum of
+    their lengths.  Returns {n: total}."""
+    out = {}
+    for n in OFFSET_COUNTS:
+        text, pieces, dest = offsets_case(n)
+        data = upload_text(be, text)
+        recs, _, nlines, err = be.fastq_index(data, len(text))
+        _sync(be)
+        assert nlines == 4 * n and recs.shape[0] == n and err == INT64_MAX, n
+        want = b"".join(p for p, keep in zip(pieces, dest.tolist()) if keep)
+        sizes = np.asarray([len(p) for p in pieces], dtype=np.int64) * dest
+        want_offs = np.concatenate((np.zeros(1, np.int64), np.cumsum(sizes)))
+        begin = torch.zeros((n,), dtype=torch.int32, device=be.device)
+        end = recs[:, 3].to(torch.int32).contiguous()                           # the whole sequence: seq_len
+        offs, got, intact = emit_call(be, data, recs, begin, end, None, None, _u8(be, dest), 1, 0)
+        assert offs[n] == len(want), (n, offs[n], len(want))                   # the total
+        assert np.array_equal(np.asarray(offs, dtype=np.int64), want_offs), n
+        assert intact, ("guard bytes overwritten", n)
+        assert got == want, n
+        out[n] = offs[n]
+    return out
+
+
 def _render(lines):
     """[(content, eol)] -> text.  A lone "\\r" followed by an empty line that ends in "\\n" would read as one
     "\\r\\n": such a line gets "\\r\\n" of its own."""

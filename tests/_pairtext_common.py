@@ -1,5 +1,5 @@
 """Shared by test_pairtext_host.py (the CPU twin, tests/emu/emu_pairtext.cpp) and test_gpu_pairtext.py (the kernels of
-atropos_amd/csrc/fastq_kernels.hip): the pair formatter ``atr_fastq_emit_pairs`` at the C ABI against the plain
+atropos_amd/csrc/pairtext_kernels.hip): the pair formatter ``atr_fastq_emit_pairs`` at the C ABI against the plain
 Python model of ``_fastq_kernels_common`` (``model_format`` of the interleaved record list), and the interleaved
 file drivers against the reference's files (tests/golden/pairtext.json.gz).
 

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: CPU twin of the grouped formatter and the group codes of
-// atropos_amd/csrc/fastq_kernels.hip (atr_fastq_emit_grouped, atr_demux_groups), built from the same
+// atropos_amd/csrc/fastq_emit_kernels.hip (atr_fastq_emit_grouped, atr_demux_groups), built from the same
 // per-record source (demux_core.hpp, fastq_core.hpp) with -DATR_HOST_EMU.  A harness for the pipeline's
 // CPU tests, not parity evidence for the kernels: the positions are made with plain running sums here.
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: CPU twin of atropos_amd/csrc/fastq_kernels.hip, built from the same
+// TEST INFRASTRUCTURE: CPU twin of atropos_amd/csrc/fastq_kernels.hip and fastq_emit_kernels.hip, built from the same
 // per-record source (fastq_core.hpp, locate_core.hpp::pack_word) with -DATR_HOST_EMU so that
 // the CPU test-suite can check the FASTQ batch logic without a GPU.  One loop iteration
 // here = one thread (or one wave iteration) of the kernel of the same name.

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: CPU twin of the pair formatter of atropos_amd/csrc/fastq_kernels.hip
+// TEST INFRASTRUCTURE: CPU twin of the pair formatter of atropos_amd/csrc/pairtext_kernels.hip
 // (atr_fastq_emit_pairs), built from the same per-pair source (pairtext_core.hpp over fastq_core.hpp) with
 // -DATR_HOST_EMU.  One loop iteration here = one pair of the kernel's byte-per-lane path, with one lane.
 #include <stdint.h>

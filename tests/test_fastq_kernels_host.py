@@ -46,6 +46,12 @@ def test_formatter_stage_limit(emu_backend):
         assert (tiles["staged"], tiles["overflow"], tiles["need_in"]) == (1, 1, [stage, stage + 1])
 
 
+def test_formatter_offsets_at_the_scan_edges(emu_backend):
+    """(The twin's offsets are a serial sum: this run proves the model and the case builder.)"""
+    rep = K.check_emit_offsets(emu_backend)
+    assert tuple(rep) == K.OFFSET_COUNTS and rep[0] == 0 and all(rep[n] > 0 for n in K.OFFSET_COUNTS[2:])
+
+
 def test_index_newlines_on_block_boundaries(emu_backend):
     rep = K.check_index(emu_backend)
     assert rep["texts"] == 6 and rep["records"] > 6 * 120 and rep["errors"] == [1, 2, 3, 4]

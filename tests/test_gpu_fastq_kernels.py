@@ -1,4 +1,4 @@
-"""The kernels of atropos_amd/csrc/fastq_kernels.hip at the C ABI, with inputs of their own, against the plain Python
+"""The kernels of atropos_amd/csrc/fastq_kernels.hip and fastq_emit_kernels.hip at the C ABI, with inputs of their own, against the plain Python
 model of tests/_fastq_kernels_common.py: the launch shapes, alignments and edges that the pipelines never choose.
 Every comparison is exact.  tests/test_fastq_kernels_host.py runs the same checks on the CPU twin."""
 import pytest
@@ -8,7 +8,7 @@ from . import _fastq_kernels_common as K
 pytestmark = pytest.mark.gpu
 
 # bytes per LDS stage of the four emit_staged_kernel instantiations, by record_bytes_hint: EMIT_STAGE = 13 * 1024 in
-# fastq_kernels.hip -- <32> EMIT_STAGE, <8> EMIT_STAGE / 4, <16> EMIT_STAGE / 2, <16> EMIT_STAGE
+# fastq_device.hpp -- <32> EMIT_STAGE, <8> EMIT_STAGE / 4, <16> EMIT_STAGE / 2, <16> EMIT_STAGE
 EMIT_STAGES = {0: 13312, 300: 3328, 390: 6656, 500: 13312}
 EMIT_TILES = {0: 32, 300: 8, 390: 16, 500: 16}
 
@@ -56,6 +56,14 @@ def test_formatter_stage_limit(hip_backend):
     for hint, (fit, overflow, need_in) in rep.items():
         assert fit > 0 and overflow > 0, hint
         assert need_in == [EMIT_STAGES[hint], EMIT_STAGES[hint] + 1], hint
+
+
+def test_formatter_offsets_at_the_scan_edges(hip_backend):
+    """n = 0, 1, around one and two scan blocks, and 1 048 576 + 1025 (a run of two block totals per thread of
+    scan_sums_kernel): text, every offset and the total against the host model."""
+    rep = K.check_emit_offsets(hip_backend)
+    print(rep)
+    assert tuple(rep) == K.OFFSET_COUNTS and rep[0] == 0 and all(rep[n] > 0 for n in K.OFFSET_COUNTS[2:])
 
 
 def test_index_newlines_on_block_boundaries(hip_backend):
