@@ -220,6 +220,16 @@ PROTOTYPES = {
     "atr_detect_mark_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, STREAM]),
     "atr_detect_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, STREAM]),
     "atr_detect_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, STREAM]),
+    "atr_detect_kmer_slots": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 3 + [STREAM]),
+    "atr_detect_kmer_pair_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_int, C.c_void_p, STREAM]),
+    "atr_detect_kmer_rank_work_bytes": (C.c_size_t, [C.c_int64]),
+    "atr_detect_kmer_rank": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 6 + [C.c_size_t, STREAM]),
+    "atr_detect_kmer_level": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_void_p,
+                                                                                     C.c_void_p, C.c_int64, C.c_void_p, STREAM]),
+    "atr_detect_kmer_next": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [STREAM]),
+    "atr_detect_kmer_gather": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, STREAM]),
+    "atr_detect_kmer_support": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, STREAM]),
     "atr_report_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "atr_report_destroy": (None, [C.c_void_p]),
     "atr_report_counters": (C.c_int64, [C.c_void_p]),
@@ -253,6 +263,11 @@ GUNZIP_MAX_MEMBERS = 1 << 22             # atr_gunzip_members: members of one ca
 GZIP_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")  # atr_gzip_eof
 DETECT_MAX_READ = 320                    # atr_detect_*: reads up to here (the complexity table is (len + 1)^2 doubles)
 DETECT_HDR = 8                           # detect_core.hpp: kept, distinct, invalid, overlong, then 4 x nseq counters
+# atr_detect_kmer_* (detect_kmer_core.hpp): the envelope, the words of a candidate row and of the state block
+KMER_MIN_K, KMER_MAX_K, KMER_MAX_SLOTS, KMER_MAX_CANDIDATES, KMER_MAX_PATTERNS = 4, 32, (1 << 31) - 1, 1 << 20, 64
+KMER_C_LEVEL, KMER_C_COUNT, KMER_C_REP, KMER_C_OFFSET, KMER_C_QUIRK, KMER_C_WORDS = 0, 1, 2, 3, 4, 5
+KMER_S_CANDIDATES, KMER_S_SURVIVORS, KMER_S_OVER, KMER_S_WORDS = 0, 1, 8, 330
+KMER_NO_KEY = (1 << 63) - 1
 
 # atr_report_*: the words of the counter block (report_core.hpp), the counting modes of a trimmer stage, the variants
 REPORT_IN_RECORDS, REPORT_IN_BASES, REPORT_WITH_ADAPTERS, REPORT_OVERFLOW = 0, 1, 2, 3
@@ -1079,7 +1094,94 @@ class BamCalls(object):
         return text, total, used, err, offsets[:used + 1]
 
 
-class HipBackend(AbiCalls, PairTextCalls, StatsCalls, FastaCalls, GunzipStreamCalls, BamCalls):
+class KmerCalls(object):
+    """The wrappers of the de-novo discovery entry points (atr_detect_kmer_*), written against ``_call`` / ``_host`` /
+    ``empty`` like ``AbiCalls``' methods.  A mixin of its own: the CPU test-suite serves these entry points from a twin
+    library of their own (tests/emu/emu_kmer.cpp)."""
+
+    def detect_kmer_slots(self, records, kept, reps, start, total, kmer_size):
+        """reps / start: int64 [nrep].  (table of representatives int64 [nrep, 3], slot_rep int32 [total], level int32
+        [nrep])."""
+        nrep = int(reps.shape[0])
+        tab = self.empty((max(nrep, 1), 3), torch.int64)
+        slot_rep = self.empty((max(int(total), 1),), torch.int32)
+        level = self.empty((max(nrep, 1),), torch.int32)
+        self._call("atr_detect_kmer_slots", _ptr(records), _ptr(kept), _ptr(reps), _ptr(start), nrep, int(total), int(kmer_size),
+                   _ptr(tab), _ptr(slot_rep), _ptr(level))
+        return tab, slot_rep[:int(total)], level[:nrep]
+
+    def detect_kmer_pair_keys(self, tab, slot_rep, data, id_a, a, id_b, b):
+        """int64 keys [slots] of the (a + b)-mers (``None`` for the classes of 1-mers: the bytes)."""
+        total = int(slot_rep.shape[0])
+        keys = self.empty((max(total, 1),), torch.int64)
+        self._call("atr_detect_kmer_pair_keys", _ptr(tab), _ptr(slot_rep), total, _ptr(data), _ptr(id_a), int(a), _ptr(id_b), int(b),
+                   _ptr(keys))
+        return keys[:total]
+
+    def detect_kmer_rank(self, keys, idx, slot_list, cls):
+        """``keys`` sorted, ``idx`` where each came from, ``slot_list`` (or None) the slot of an entry; writes ``cls``
+        at the slots.  (begin, end, head int32 [n], nclasses int64 [1] on the device)."""
+        n = int(keys.shape[0])
+        begin, end, head = (self.empty((max(n, 1),), torch.int32) for _ in range(3))
+        nclasses = self.empty((1,), torch.int64)
+        need = self._host("atr_detect_kmer_rank_work_bytes", n)
+        work = self.empty((max(need, 16),), torch.uint8)
+        self._call("atr_detect_kmer_rank", _ptr(keys), _ptr(idx), _ptr(slot_list), n, _ptr(cls), _ptr(begin), _ptr(end), _ptr(head),
+                   _ptr(nclasses), _ptr(work), work.numel())
+        return begin, end, head, nclasses
+
+    def detect_kmer_state(self, capacity):
+        """(zeroed state block int64 [KMER_S_WORDS], candidate table int32 [capacity, KMER_C_WORDS])."""
+        state = self.empty((KMER_S_WORDS,), torch.int64)
+        state.zero_()
+        return state, self.empty((max(int(capacity), 1), KMER_C_WORDS), torch.int32)
+
+    def detect_kmer_level(self, tab, slot_rep, slot_list, n, cls, cls_prev, classes, cand_of_prev, k, min_count, level, cand,
+                          capacity, state):
+        """One level; returns cand_of int32 [n] (class -> its row or -1)."""
+        begin, end, head = classes
+        cand_of = self.empty((max(int(n), 1),), torch.int32)
+        self._call("atr_detect_kmer_level", _ptr(tab), _ptr(slot_rep), _ptr(slot_list), int(n), _ptr(cls), _ptr(cls_prev),
+                   _ptr(begin), _ptr(end), _ptr(head), _ptr(cand_of), _ptr(cand_of_prev), int(k), int(min_count), _ptr(level),
+                   _ptr(cand), int(capacity), _ptr(state))
+        return cand_of
+
+    def detect_kmer_next(self, tab, slot_rep, slot_list, n, cls, data, level, k, state):
+        """(list_next int32 [n], keys_next int64 [n]); how many are filled is word KMER_S_SURVIVORS of ``state``."""
+        list_next = self.empty((max(int(n), 1),), torch.int32)
+        keys_next = self.empty((max(int(n), 1),), torch.int64)
+        self._call("atr_detect_kmer_next", _ptr(tab), _ptr(slot_rep), _ptr(slot_list), int(n), _ptr(cls), _ptr(data), _ptr(level),
+                   int(k), _ptr(list_next), _ptr(keys_next), _ptr(state))
+        return list_next, keys_next
+
+    def detect_kmer_gather(self, tab, nrep, data, cand, text_off):
+        """The texts of the rows of ``cand`` back to back (uint8); text_off int64 [rows + 1] on the device."""
+        ncand = int(text_off.shape[0]) - 1
+        out = self.empty((max(int(text_off[-1].item()), 1),), torch.uint8)
+        self._call("atr_detect_kmer_gather", _ptr(tab), int(nrep), _ptr(data), _ptr(cand), _ptr(text_off), ncand, _ptr(out))
+        return out
+
+    def detect_kmer_support(self, tab, nrep, data, level, patterns):
+        """patterns: list of bytes (at most KMER_MAX_PATTERNS, each at most DETECT_MAX_READ).  (abundance int64 [P],
+        longest uint64 words as int64 [P]) on the host."""
+        npat = len(patterns)
+        mat = np.zeros((max(npat, 1), DETECT_MAX_READ), dtype=np.uint8)
+        lens = np.zeros((max(npat, 1),), dtype=np.int32)
+        for i, p in enumerate(patterns[:KMER_MAX_PATTERNS]):
+            if len(p) > DETECT_MAX_READ:
+                raise AtroposUnsupported("atr_detect_kmer_support: a pattern of %d bytes (at most %d)" % (len(p), DETECT_MAX_READ))
+            mat[i, :len(p)] = np.frombuffer(p, dtype=np.uint8)
+            lens[i] = len(p)
+        d_mat = torch.from_numpy(mat).to(self.device)
+        d_lens = torch.from_numpy(lens).to(self.device)
+        abundance = self.empty((max(npat, 1),), torch.int64)
+        longest = self.empty((max(npat, 1),), torch.int64)
+        self._call("atr_detect_kmer_support", _ptr(tab), int(nrep), _ptr(data), _ptr(level), _ptr(d_mat), _ptr(d_lens), npat,
+                   _ptr(abundance), _ptr(longest))
+        return abundance[:npat].cpu().numpy(), longest[:npat].cpu().numpy()
+
+
+class HipBackend(AbiCalls, PairTextCalls, StatsCalls, FastaCalls, GunzipStreamCalls, BamCalls, KmerCalls):
     """Thin object view of the C ABI; all buffers are torch tensors on one GPU.  The calls the CPU test-suite's stand-in
     serves as well are ``AbiCalls``'; here are the plumbing under them and the device-only calls."""
 

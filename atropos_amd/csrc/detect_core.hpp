@@ -163,11 +163,12 @@ struct DetectTables {
 };
 
 // Returns 0, -1 (invalid) or -2 (outside the envelope).  seqs: the known sequences back to back, lens[nseq].
+// nseq == 0 (the heuristic detector's filter: no known list, no shortest-known-sequence test) builds empty tables.
 static inline int det_build(DetectTables &T, const uint8_t *seqs, const int32_t *lens, int nseq, int kmer_size,
                             const uint8_t *past, int npast, const int32_t *thresholds, const double *complexity,
                             int max_len) {
-    if (nseq < 1 || !seqs || !lens || !thresholds || !complexity || npast < 0 || (npast && !past) || kmer_size < 1 ||
-        max_len < 1)
+    if (nseq < 0 || (nseq && (!seqs || !lens || !thresholds)) || !complexity || npast < 0 || (npast && !past) ||
+        kmer_size < 1 || max_len < 1)
         return -1;
     if (nseq > DET_MAX_SEQS || npast > DET_MAX_PAST_END || kmer_size < DET_MIN_K || kmer_size > DET_MAX_K ||
         max_len > DET_MAX_READ)
@@ -175,14 +176,16 @@ static inline int det_build(DetectTables &T, const uint8_t *seqs, const int32_t 
     T.nseq = nseq; T.kmer_size = kmer_size; T.npast = npast; T.max_len = max_len;
     for (int i = 0; i < npast; ++i) T.past[i] = past[i];
     T.seq_off.assign(1, 0u);
-    T.min_k = 0x7fffffff;
+    T.min_k = nseq ? 0x7fffffff : 0;
     for (int s = 0; s < nseq; ++s) {
         if (lens[s] < 0) return -1;
         T.seq_off.push_back(T.seq_off.back() + (uint32_t)lens[s]);
         if (lens[s] < T.min_k) T.min_k = lens[s];
     }
-    T.seq_bytes.assign(seqs, seqs + T.seq_off.back());
-    T.thresholds.assign(thresholds, thresholds + nseq);
+    if (nseq) {
+        T.seq_bytes.assign(seqs, seqs + T.seq_off.back());
+        T.thresholds.assign(thresholds, thresholds + nseq);
+    }
     T.complexity.assign(complexity, complexity + (size_t)(max_len + 1) * (max_len + 1));
     // the alphabet: the bytes of the known sequences and their complements
     bool used[256] = {false};

@@ -333,6 +333,7 @@ int atr_detect_batch(const void *handle, const uint8_t *d_bytes, const atr_fastq
                      const int64_t *d_order, const uint8_t *d_rep, int64_t m, void *d_counters, void *stream) {
     const DetectHandle *h = (const DetectHandle *)handle;
     if (!h || m < 0) return ATR_ERR_INVALID;
+    if (h->T.nseq == 0) return ATR_ERR_UNSUPPORTED;                    // a detector without known sequences: no match pass
     if (m == 0) return ATR_OK;
     if (!d_bytes || !d_records || !d_kept || !d_order || !d_rep || !d_counters) return ATR_ERR_INVALID;
     hipLaunchKernelGGL(det_match_kernel, dim3(det_grid(m)), dim3(256), h->lds, (hipStream_t)stream, h->D, d_bytes,

@@ -851,6 +851,62 @@ int atr_detect_batch(const void *detect, const uint8_t *d_bytes, const atr_fastq
 int atr_detect_read(const void *detect, const void *d_counters, uint64_t *out, void *stream);
 
 
+/* De-novo adapter discovery (HeuristicDetector._get_contaminants, commands/detect/__init__.py:568-619; atropos detect
+ * --detector heuristic) over the representatives the filter and the distinct pass of atr_detect_* leave.  A detector
+ * made by atr_detect_create with nseq == 0 filters without the shortest-known-sequence test; atr_detect_batch refuses
+ * such a detector (ATR_ERR_UNSUPPORTED).
+ *
+ * Every kept base of every representative is a slot; the slots of a read are consecutive (d_start[j]: the first slot
+ * of representative j, the exclusive prefix sum of their kept lengths; total: their sum).  A k-mer is known by its
+ * class, the dense rank of its text among the k-mers counted at that length (int32; KMER_NO_CLASS = -1 where the slot
+ * has no room for k bytes).  Keys are 64-bit integers the caller sorts; nothing is hashed.
+ *
+ *   atr_detect_kmer_slots      d_reps[nrep]: the records of the representatives.  Writes the table of representatives
+ *                              (nrep x 24 bytes), d_slot_rep[total] and d_level[nrep] = kmer_size.
+ *   atr_detect_kmer_pair_keys  d_keys[p] = (class of the a-mer at p) << 32 | (class of the b-mer at p + a), or
+ *                              INT64_MAX without room for a + b bytes.  A null class array (a or b == 1) is the bytes.
+ *   atr_detect_kmer_rank       d_keys[n] sorted ascending, d_idx[n] the entry each came from, d_list (or null: the
+ *                              entry is the slot) its slot.  d_cls[slot] = dense rank of the key; per class its run
+ *                              d_begin / d_end in the sorted order (count = end - begin) and d_head, the smallest slot that
+ *                              holds it; *d_nclasses.  d_work: atr_detect_kmer_rank_work_bytes(n) bytes.
+ *   atr_detect_kmer_level      one level k over the n surviving slots (d_list or null: all slots): a class with
+ *                              count > min_count is over-represented: level[read] = k + 1 for the reads that hold one,
+ *                              a row (level, count, representative and offset of the first occurrence, quirk = 0) in d_cand (int32 x 5, at most
+ *                              `capacity` rows are written; d_state[0] counts all), d_cand_of[class] = its row or -1,
+ *                              d_state[8 + k] = over-represented classes.  With the classes of level k - 1 (d_cls_prev,
+ *                              d_cand_of_prev) a read of exactly k bases whose text is over-represented sets the quirk
+ *                              word of the rows of its two (k - 1)-mers.
+ *   atr_detect_kmer_next       after it: the slots of reads with level == k + 1 and room for k + 1 bytes into
+ *                              d_list_next with d_keys_next = class << 8 | next byte; d_state[1] = how many.
+ *   atr_detect_kmer_gather     the texts of ncand rows, row c at d_text_off[c] .. d_text_off[c + 1] of d_out.
+ *   atr_detect_kmer_support    npat patterns (npat x 320 bytes, d_pat_len): d_abundance[p] = representatives that hold
+ *                              pattern p; d_longest[p] = min over the representatives with level >= len(p) that hold it
+ *                              of (first index << 32 | record), all ones if none.
+ * d_state: 330 int64 words, zeroed by the caller.  ATR_ERR_UNSUPPORTED, before anything is launched: kmer_size outside
+ * 4 .. 32, 2^31 slots or more, a k-mer longer than 320, capacity above 2^20, more than 64 patterns. */
+int atr_detect_kmer_slots(const atr_fastq_record *d_records, const int32_t *d_kept, const int64_t *d_reps,
+                          const int64_t *d_start, int64_t nrep, int64_t total, int kmer_size, void *d_reptab,
+                          int32_t *d_slot_rep, int32_t *d_level, void *stream);
+int atr_detect_kmer_pair_keys(const void *d_reptab, const int32_t *d_slot_rep, int64_t total, const uint8_t *d_bytes,
+                              const int32_t *d_id_a, int a, const int32_t *d_id_b, int b, int64_t *d_keys, void *stream);
+size_t atr_detect_kmer_rank_work_bytes(int64_t n);
+int atr_detect_kmer_rank(const int64_t *d_keys, const int64_t *d_idx, const int32_t *d_list, int64_t n, int32_t *d_cls,
+                         int32_t *d_begin, int32_t *d_end, int32_t *d_head, int64_t *d_nclasses, void *d_work,
+                         size_t work_bytes, void *stream);
+int atr_detect_kmer_level(const void *d_reptab, const int32_t *d_slot_rep, const int32_t *d_list, int64_t n,
+                          const int32_t *d_cls, const int32_t *d_cls_prev, const int32_t *d_begin, const int32_t *d_end,
+                          const int32_t *d_head, int32_t *d_cand_of, const int32_t *d_cand_of_prev, int k, int64_t min_count,
+                          int32_t *d_level, int32_t *d_cand, int64_t capacity, int64_t *d_state, void *stream);
+int atr_detect_kmer_next(const void *d_reptab, const int32_t *d_slot_rep, const int32_t *d_list, int64_t n,
+                         const int32_t *d_cls, const uint8_t *d_bytes, const int32_t *d_level, int k, int32_t *d_list_next,
+                         int64_t *d_keys_next, int64_t *d_state, void *stream);
+int atr_detect_kmer_gather(const void *d_reptab, int64_t nrep, const uint8_t *d_bytes, const int32_t *d_cand,
+                           const int64_t *d_text_off, int64_t ncand, uint8_t *d_out, void *stream);
+int atr_detect_kmer_support(const void *d_reptab, int64_t nrep, const uint8_t *d_bytes, const int32_t *d_level,
+                            const uint8_t *d_patterns, const int32_t *d_pat_len, int npat, int64_t *d_abundance,
+                            uint64_t *d_longest, void *stream);
+
+
 /* The trim report: summary['trim'] of the reference (RecordHandler.summarize, commands/trim/__init__.py:129-137) and
  * the input totals, counted on the device while the trim pipeline runs.
  *
